@@ -16,15 +16,22 @@ N = 8 -- and the line says what RCCL saw (rccl_ranks), how the stream was stitch
 stream is the oracle's (committed digests, tests/golden/config5_digest*.json).  --virtual: the N ranks share the GPUs the box has
 (gloo carries the exchanges) -- the dry run of a one-GPU box.  --single-process: the same sharding inside ONE call of the C ABI.
 
-Besides the contract's fields the line carries: value_host_api (the drop-in call on pinned host buffers,
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it makes the input, sets up,
+warms up, times the N steps and prints the line -- value, ms_per_step, and what the timed steps' own clocks say (stage_ms,
+step_ms_events, roofline.achieved / kernel_ms / input_load).  --dump-outputs DIR writes the stream the last timed step made
+(its length and a fixed, seeded sample of its bytes, see dump_outputs) so that two builds can be compared output for output.
+
+--full adds everything that takes runs or checks of its own: value_host_api (the drop-in call on pinned host buffers,
 H2D and D2H inside the timed region), value_host_api_pageable (the same call on the memory a drop-in caller has: a plain
-bytearray in and out -- the context's host threads carry it; beside it the runtime's own copies, MI355_CFG_HOST_BOUNCE = 0), roofline.input_load (achieved HBM GB/s of the kernel that reads
-the input coalesced), roofline.lds_bank_conflict_rate of the match compare and roofline.valu_issue (wave
-instructions per input byte and the share of the SIMDs' cycles they take: what the dominant kernel is bound
-by; from counters taken in the run, else from the committed PMC file),
-value_as_called (the timed steps once more as a caller's context runs them: without the per-stage clocks this bench asks for -- five
-events, 29 us of idle queue, in every timed step), small_call (the reference's 167 KB fixture pg11.txt: wall clock of one resident call and of one host-buffer call on pageable memory,
-against the oracle), cpu_baseline as the median of five runs with its all-cores and zlib companions.
+bytearray in and out -- the context's host threads carry it; beside it the runtime's own copies, MI355_CFG_HOST_BOUNCE = 0), roofline.traffic,
+roofline.lds_bank_conflict_rate of the match compare and roofline.valu_issue (wave instructions per input byte and the share of
+the SIMDs' cycles they take: what the dominant kernel is bound by; from counters taken in the run, else from the committed PMC
+file -- a plain run reads only the file), value_as_called (the timed steps once more as a caller's context runs them: without
+the per-stage clocks this bench asks for -- five events, 29 us of idle queue, in every timed step), small_call (the reference's
+167 KB fixture pg11.txt: wall clock of one resident call and of one host-buffer call on pageable memory, against the oracle),
+cpu_baseline as the median of five runs with its all-cores and zlib companions, bit_exact_vs_oracle (the stream against the
+oracle's, or a committed digest of it, for N > 1), and for N > 1 rank 0's phases of one step synchronised per phase.
+--no-cpu-baseline / --no-host-api / --no-live-pmc leave single legs of --full out.
 """
 import argparse
 import json
@@ -39,22 +46,28 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
-ENWIK8_PATHS = [os.environ.get("MI355_ENWIK8", ""), os.path.join(ROOT, "data", "enwik8"), "/data/enwik8"]
+ENWIK8_FILE = [""]  # --enwik8 PATH: the real corpus, named on the command line (the same arguments make the same input)
 INPUT_NOTE = {}
+DUMP_WHOLE = 12 << 20    # --dump-outputs: a stream up to this many bytes is written whole (48 MB as float32) ...
+DUMP_SAMPLE = 3 << 20    # ... a longer one as its first and last DUMP_EDGE bytes and this many seeded positions between
+DUMP_EDGE = 256 << 10
+DUMP_SEED = 0x44554D50
 
 
 def make_input(workload, size, rank):
     import datagen
     if workload == "enwik8":
-        # the real enwik8 when the box has it (there is no network to fetch it: data/enwik8 or
-        # $MI355_ENWIK8), else enwik8-like synthetic text of the same size; the bench line says which
-        for p in ENWIK8_PATHS:
-            if p and os.path.isfile(p) and os.path.getsize(p) >= size * (rank + 1):
-                with open(p, "rb") as f:
-                    f.seek(size * rank)
-                    INPUT_NOTE["enwik8"] = "the real enwik8 (%s)" % p
-                    return f.read(size)
-        INPUT_NOTE["enwik8"] = "enwik8-like synthetic text (tests/datagen.py text_like; no data/enwik8 on this box)"
+        # the real enwik8 when --enwik8 names it (there is no network to fetch it), else enwik8-like
+        # synthetic text of the same size; the bench line says which
+        p = ENWIK8_FILE[0]
+        if p:
+            if not os.path.isfile(p) or os.path.getsize(p) < size * (rank + 1):
+                raise SystemExit("--enwik8 %s: not a file of at least %d bytes" % (p, size * (rank + 1)))
+            with open(p, "rb") as f:
+                f.seek(size * rank)
+                INPUT_NOTE["enwik8"] = "the real enwik8 (%s)" % p
+                return f.read(size)
+        INPUT_NOTE["enwik8"] = "enwik8-like synthetic text (tests/datagen.py text_like; --enwik8 PATH takes the real file)"
         return datagen.text_like(size, 0x656E77696B38 ^ rank)
     if workload == "zeros":
         return bytes(size)
@@ -124,6 +137,29 @@ def cpu_baselines(data, olvl, level_name):
                           "sample": "first %d bytes in %d chunks, one oracle encoder per core (chunk-exact, P2)" % (
                               len(big), len(chunks))},
             "zlib6_anchor": {"value": round(z6, 2), "unit": "MB/s", "cores": 1, "note": "system zlib -6, not the reference"}}
+
+
+def dump_outputs(dirname, stream, n):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- the compressed stream, `stream`
+    (a uint8 tensor, device or host) of `n` bytes -- as DIR/stream_len.npy (float64 [n]) and DIR/stream_bytes.npy (float32).
+    A stream of at most DUMP_WHOLE bytes is written whole; a longer one as its first and last DUMP_EDGE bytes and
+    DUMP_SAMPLE positions drawn with a fixed seed, whose offsets go to DIR/stream_index.npy (float64): at most 48 MB in all.
+    A difference anywhere in a bit-packed stream moves the bits after it, so the sample sees it."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = stream[:n].cpu().numpy() if n else np.zeros(0, dtype=np.uint8)
+    for f in ("stream_len.npy", "stream_bytes.npy", "stream_index.npy"):
+        if os.path.exists(os.path.join(dirname, f)):
+            os.remove(os.path.join(dirname, f))
+    np.save(os.path.join(dirname, "stream_len.npy"), np.array([n], dtype=np.float64))
+    if n <= DUMP_WHOLE:
+        np.save(os.path.join(dirname, "stream_bytes.npy"), host.astype(np.float32))
+        return
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(np.concatenate([np.arange(DUMP_EDGE), np.arange(n - DUMP_EDGE, n),
+                                    rng.integers(0, n, DUMP_SAMPLE)]))
+    np.save(os.path.join(dirname, "stream_bytes.npy"), host[idx].astype(np.float32))
+    np.save(os.path.join(dirname, "stream_index.npy"), idx.astype(np.float64))
 
 
 def single_process(args):
@@ -198,6 +234,8 @@ def single_process(args):
     for d in set(devs):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, n)
     tr = {k: round(sum(t[k] for t in traces) / len(traces), 4) for k in traces[0]}
     algo = size + n // N
     k_ms = sum(mm) / len(mm)
@@ -225,7 +263,8 @@ def single_process(args):
     def parts():
         for i in range(0, n, 256 << 20):
             yield bytes(d_out[i:min(n, i + (256 << 20))].cpu().numpy())
-    res.update(stream_check(args.workload, total, size, N, lvl, parts, n))
+    if args.full:
+        res.update(stream_check(args.workload, total, size, N, lvl, parts, n))
     m.close()
     print(json.dumps(res))
     quiet_stdout()
@@ -307,7 +346,7 @@ def live_pmc(args, size, lvl, dominant):
     t0 = time.perf_counter()
     for counters in passes:
         d = tempfile.mkdtemp(prefix="mi355_pmc_", dir="/tmp")
-        cmd = [exe, "--pmc"] + counters + ["--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--steps", "1",
+        cmd = [exe, "--pmc"] + counters + ["--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "1",
                                            "--warmup", "0", "--no-cpu-baseline", "--no-host-api", "--no-live-pmc", "--workload", args.workload,
                                            "--size", str(size), "--level", lvl]
         try:
@@ -396,9 +435,20 @@ def main(argv=None):
                                                     "newest profiles/r*_pmc_summary.json)")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not run the three rocprofv3 --pmc passes that measure roofline.traffic / valu_issue on this box (about a minute)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs or checks of their own (value_as_called, value_host_api*, small_call, live "
+                         "counters, cpu_baseline, bit_exact_vs_oracle; N > 1: the stream check and rank 0's phases); a plain run "
+                         "only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the stream the last one made to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--enwik8", default="", metavar="PATH",
+                    help="workload enwik8: take its bytes from this file (the real corpus) instead of the synthetic text")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    ENWIK8_FILE[0] = args.enwik8
     args.virtual = args.virtual or os.environ.get("MI355_BENCH_VIRTUAL") == "1"
     if not args.workload:
         args.workload = "enwik8" if args.gpus == 1 else "webtext"
@@ -537,7 +587,7 @@ def main(argv=None):
             for k, v in info["stage_ms"].items():
                 stage_ms[k] = stage_ms.get(k, 0.0) + v
         if world > 1:
-            shard.stitch(d_out if cdev == "cuda" else d_out.cpu(), n, rank, world)
+            last_img[0] = shard.stitch(d_out if cdev == "cuda" else d_out.cpu(), n, rank, world)[0]  # (rank 0: the chunks gathered)
 
     for _ in range(args.warmup):
         step(False)
@@ -551,10 +601,15 @@ def main(argv=None):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # (N = 1: the same steps once more as a caller's context runs them -- without the per-stage clocks this bench asks for, which
-    # are five events, 29 us of idle queue, in every step above: value_as_called)
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            dump_outputs(args.dump_outputs, d_out, out_len[0])
+        else:
+            dump_outputs(args.dump_outputs, last_img[0], last_img[0].numel())
+    # (N = 1, --full: the same steps once more as a caller's context runs them -- without the per-stage clocks this bench asks for,
+    # which are five events, 29 us of idle queue, in every step above: value_as_called)
     elapsed_plain = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             ctx.config(da.Context.CFG_STAGE_CLOCKS, 0)
             step(False)
@@ -569,7 +624,7 @@ def main(argv=None):
             elapsed_plain = None
     p1_trace = None
     rccl_ranks = 0
-    if shard_mode == "p1":  # one more step, untimed, with a device synchronisation after every phase
+    if shard_mode == "p1" and args.full:  # one more step, untimed, with a device synchronisation after every phase
         img, _ = shard.encode_p1_dist(da, ctx, d_ext, layout, total, rank, world, options, comm_device=cdev, trace=True)
         last_img[0] = img
         p1_trace = dict(shard.LAST_TRACE)
@@ -606,7 +661,7 @@ def main(argv=None):
         pmc_source = None
         valu_issue = None
         live = None
-        if world == 1 and not args.no_live_pmc and dominant in ("k_match3", "k_rle"):
+        if world == 1 and args.full and not args.no_live_pmc and dominant in ("k_match3", "k_rle"):
             live = live_pmc(args, size, lvl, dominant)
         if live is not None:
             traffic = live["hbm_bytes"]
@@ -686,14 +741,14 @@ def main(argv=None):
             res["rccl_ranks"] = rccl_ranks  # (0: the exchanges did not travel over RCCL -- the gloo dry run)
             res["stitch"] = "rccl" if backend == "nccl" else backend
             res["devices"] = torch.cuda.device_count()
-            if shard_mode == "p1" and last_img[0] is not None:
+            if shard_mode == "p1" and last_img[0] is not None and args.full:
                 img = last_img[0]
 
                 def parts():
                     for i in range(0, total_out, 256 << 20):
                         yield bytes(img[i:min(total_out, i + (256 << 20))].cpu().numpy())
                 res.update(stream_check(args.workload, total, size, world, lvl, parts, total_out))
-        if world == 1 and not args.no_host_api:
+        if world == 1 and args.full and not args.no_host_api:
             # the drop-in call itself, deflate_bytes(&[u8]) -> Vec<u8> (src/lib.rs:163): pinned host buffers,
             # first H2D byte to last D2H byte inside the timed region
             h_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory()
@@ -716,7 +771,7 @@ def main(argv=None):
                                              "kernels and the copy engine's D2H overlap)",
                                      "same_bytes": bool(hn == out_len[0] and torch.equal(
                                          h_out[:hn], d_out[:hn].cpu()))}
-        if world == 1 and not args.no_host_api:
+        if world == 1 and args.full and not args.no_host_api:
             # ... and on the memory a drop-in caller has (src/lib.rs:137-147: &[u8] in, Vec<u8> out): plain pageable buffers.
             # The context's host threads carry them through page-locked slots (MI355_CFG_HOST_BOUNCE, deflate_bounce.inc);
             # beside it the same call with the threads off -- the runtime's own copies, one after the other
@@ -748,7 +803,7 @@ def main(argv=None):
                             "first byte in to last byte out; host_path bits: 1 pieces, 2 input by the context's host threads, 4 output by them")
             fast["runtime_copies"] = slow  # (MI355_CFG_HOST_BOUNCE = 0: what such a caller got before)
             res["value_host_api_pageable"] = fast
-        if world == 1 and not args.no_host_api:
+        if world == 1 and args.full and not args.no_host_api:
             # ... and what a SMALL call costs (the reference's own consumers -- a PNG's rows -- live there): the reference's
             # fixture pg11.txt, 167 KB, resident and through the host-buffer call on pageable memory, wall clock, the
             # context as a caller gets it (no per-stage events: MI355_CFG_STAGE_CLOCKS)
@@ -783,7 +838,7 @@ def main(argv=None):
                                      "same_bytes": bool(bytes(h_o[:sn[0]]) == bytes(s_out[:sn[0]].cpu().numpy()))}
                 small_got = bytes(h_o[:sn[0]])
                 sctx.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             import oracle_binding as ob
             olvl = {"default": ob.DEFAULT, "best": ob.BEST, "fast": ob.FAST, "rle": ob.RLE,
                     "huffman_only": ob.HUFFMAN_ONLY}[lvl]

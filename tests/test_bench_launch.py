@@ -72,3 +72,33 @@ def test_self_launch_reaches_the_device_check():
     assert out.returncode != 0
     assert "bench.py needs a GPU" in out.stderr, out.stderr[-2000:]
     assert "dry run: 2 ranks" in out.stderr
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a short stream whole, a long one as its two ends and a seeded sample (the same positions every run),
+    float32 bytes and float64 length / offsets, under 64 MB"""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    for n in (0, 70_001, bench.DUMP_WHOLE + 12345):
+        t = torch.randint(0, 256, (n + 64,), dtype=torch.uint8, generator=g)
+        for d in (tmp_path / "a", tmp_path / "b"):
+            bench.dump_outputs(str(d), t, n)
+        got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+        assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) < 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert got["stream_len.npy"].tolist() == [n]
+        b = got["stream_bytes.npy"]
+        assert b.dtype == np.float32
+        if n <= bench.DUMP_WHOLE:
+            assert "stream_index.npy" not in got and np.array_equal(b, t[:n].numpy())
+        else:
+            i = got["stream_index.npy"].astype(np.int64)
+            assert np.array_equal(i, np.load(tmp_path / "b" / "stream_index.npy").astype(np.int64))
+            assert i[0] == 0 and i[-1] == n - 1 and np.all(np.diff(i) > 0) and len(i) > bench.DUMP_SAMPLE // 2
+            assert np.array_equal(b, t[:n].numpy()[i])
+
+
+def test_plain_run_refuses_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr

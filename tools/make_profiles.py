@@ -1,7 +1,7 @@
 """Run on the GPU box from the repo root: the rocprofv3 evidence behind the bench line.
   python tools/make_profiles.py TAG        -> gpurun_out/TAG_kernel_stats.txt, TAG_pmc_summary.json, TAG_bench.json
 (copy them into profiles/).  Kernel trace and the counter passes are separate runs of the same command,
-`python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-api` (trace) / `--steps 1 --warmup 0` (counters:
+`python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-api` (trace) / `--steps 1 --warmup 0` (counters:
 one launch of every kernel, all of one shape -- the host-API leg, which launches the match kernels on pieces of
 the input, is off; the summary records the launch count per kernel and bench.py refuses a file where it differs);
 FETCH_SIZE and WRITE_SIZE in passes of their own, FETCH_SIZE doubled (MI355X_MICROARCH.md, HBM section)."""
@@ -33,7 +33,7 @@ def rocprof(args, sub):
     d = os.path.join(OUT, "%s_%s" % (TAG, sub))
     subprocess.run("rm -rf " + d, shell=True)
     cmd = ["rocprofv3"] + args + ["--output-format", "csv", "-d", d, "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                                  "--no-cpu-baseline", "--no-host-api", "--no-live-pmc"] + EXTRA
+                                  "--full", "--no-cpu-baseline", "--no-host-api", "--no-live-pmc"] + EXTRA
     subprocess.run(cmd, cwd="/tmp", env=ENV, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
     return d
 
@@ -62,7 +62,7 @@ def main():
     f = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)[0]
     rows = list(csv.DictReader(open(f)))
     with open(os.path.join(OUT, TAG + "_kernel_stats.txt"), "w") as o:
-        o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-api %s\n" % " ".join(base_extra))
+        o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-api %s\n" % " ".join(base_extra))
         o.write("%-28s %6s %12s %12s %12s %8s\n" % ("kernel", "calls", "avg_us", "min_us", "max_us", "pct"))
         for r in rows:
             o.write("%-28s %6s %12.1f %12.1f %12.1f %8.2f\n" % (short(r["Name"])[:28], r["Calls"], float(r["AverageNs"]) / 1e3,
@@ -78,7 +78,7 @@ def main():
     wr = pmc(["WRITE_SIZE"], None)
     # the bench line of an unprofiled run
     EXTRA = base_extra + ["--steps", "5", "--warmup", "2"]
-    line = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-live-pmc", "--pmc-file", "/nonexistent"] + EXTRA, capture_output=True, text=True, timeout=600).stdout.strip().splitlines()[-1]
+    line = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-live-pmc", "--pmc-file", "/nonexistent"] + EXTRA, capture_output=True, text=True, timeout=600).stdout.strip().splitlines()[-1]
     open(os.path.join(OUT, TAG + "_bench.json"), "w").write(line + "\n")
     bl = json.loads(line)
     n = bl["config"]["bytes_per_gpu"]
@@ -104,7 +104,7 @@ def main():
         kernels[k] = e
     lvl = bl["config"]["level"]
     json.dump({"note": "rocprofv3 --pmc passes (SQ set A, SQ set B, FETCH_SIZE, WRITE_SIZE: four separate runs) over `python bench.py "
-                       "--steps 1 --warmup 0 --no-cpu-baseline --no-host-api`; per launch (launches = dispatches of the kernel in a pass); hbm_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 "
+                       "--full --steps 1 --warmup 0 --no-cpu-baseline --no-host-api`; per launch (launches = dispatches of the kernel in a pass); hbm_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 "
                        "(FETCH_SIZE doubled per MI355X_MICROARCH.md); durations from the --kernel-trace run",
                "workload": bl["config"]["workload"].split(":")[0].split(" = ")[0], "bytes_per_gpu": n,
                "level": {"Compression::Default": "default", "Compression::Best": "best", "Compression::Fast": "fast", "rle()": "rle",

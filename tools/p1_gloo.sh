@@ -6,7 +6,7 @@ TAG=${1:-r03}; shift
 mkdir -p gpurun_out
 for N in 2 4 8; do
   MI355_BENCH_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 5 --warmup 2 --no-cpu-baseline "$@" \
+    --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --full --gpus $N --steps 5 --warmup 2 --no-cpu-baseline "$@" \
     2>gpurun_out/${TAG}_p1_gloo_N$N.err | tail -1 > gpurun_out/${TAG}_p1_gloo_N$N.json
   python - <<PY
 import json
