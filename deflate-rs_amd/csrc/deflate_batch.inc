@@ -1,0 +1,570 @@
+// Batched encode (include/mi355_deflate.h mi355_deflate_encode_batch[_device]): many independent inputs, one launch per stage.
+// The stages are those of a small one-shot call of run_encode (small_inits && small_tail, the speculative parse): k_sort, the walk
+// (k_match3_both), k_adv for the levels that need it, k_emit<1>, k_small_fix, k_compact, k_block_hist, k_block_header, k_plan, k_pack
+// and the zlib frame.  Every batched kernel below runs the body of its single-call kernel; the arguments come from the item's
+// descriptor (BatchItem) instead of the launch.  A launch's grid is the items' workgroups back to back, and a workgroup finds its item
+// by a search over the stage's running sums (stages.h batch_item_of).  The stages that are one workgroup per call (k_small_fix,
+// k_plan, the zlib tail) are one workgroup per item.  DESIGN.md section 10.
+namespace mi355 {
+
+struct BatchItem {
+    const uint8_t* in;
+    uint32_t n, K0, nb_max;
+    uint32_t q1_check;   // the item's first pass may fire Q1: k_small_fix stops its block stages (run_encode `speculate`)
+    uint32_t out_words;  // mi355_deflate_bound_ex(n, wrapper, 0, 0) / 4: cleared by kb_block_hist (k_pack ORs its bits in)
+    uint32_t pad;
+    uint32_t *M, *Mq;
+    uint16_t *adv, *S, *B;  // S: the sorted positions behind their pad epoch
+    uint32_t *E0, *tokbuf, *cnt, *xs, *badmap, *fixlist, *base, *tend, *pb, *bstart, *q13, *dtok, *ll_freq, *d_freq, *seg_ends;
+    BlockTab tab;
+    BlockHeader* hdr;
+    BlockPlan* plan;
+    DevState* st;  // the item's scalars and flags
+    uint8_t* out;
+};
+// the stages with a grid of their own per item (a row of running sums each)
+enum : uint32_t { BS_SORT, BS_WALK, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_N };
+struct BatchArgs {
+    const BatchItem* it;
+    const uint32_t* pre;  // BS_N rows of n_items + 1 running sums of workgroups
+    uint32_t n_items;
+};
+// the item of this workgroup, its index inside the item and the item's workgroup count in this stage
+__device__ __forceinline__ uint32_t batch_locate(const BatchArgs& a, uint32_t stage, uint32_t& local, uint32_t& count) {
+    const uint32_t* pre = a.pre + (size_t)stage * (a.n_items + 1);
+    const uint32_t i = __builtin_amdgcn_readfirstlane(batch_item_of(pre, a.n_items, blockIdx.x));
+    local = blockIdx.x - pre[i];
+    count = pre[i + 1] - pre[i];
+    return i;
+}
+__device__ __forceinline__ HashOverride batch_no_override() { return HashOverride{0, 0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr}; }
+
+template <int MODE>
+__global__ __launch_bounds__(1024) void kb_sort(BatchArgs bat_, uint32_t dbl) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_SORT, local, count)];
+    // (workgroup 0 of an item clears its scalars and sets its one segment end, as a small call's k_sort does)
+    k_sort_body<MODE>(local, it.in, it.n, batch_no_override(), it.S, it.B, 0u, dbl,
+                      SortInit{reinterpret_cast<uint32_t*>(it.st), (uint32_t)(sizeof(DevScalars) / 4), it.seg_ends, it.n});
+}
+
+// the walk of k_match3_both (both tables in one launch) at every batch size
+template <bool HAS_Q, bool SINGLE>
+__global__ __launch_bounds__(M3T) __attribute__((amdgpu_waves_per_eu(4, 4))) void kb_walk(BatchArgs bat_, uint32_t checks, uint32_t checks_q,
+                                                                                       uint32_t split) {
+    __shared__ __attribute__((aligned(256))) uint4 s_T[M3_TABLE_U4];
+    __shared__ uint32_t s_next;
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_WALK, local, count)];
+    const uint32_t e = local / split, part = local % split;
+    const SegEnds sg{it.seg_ends, 1u};
+    const int aligned16 = (reinterpret_cast<uintptr_t>(it.in) & 15) == 0 ? 1 : 0;
+    uint32_t* const ms = split == 1 ? it.tokbuf : nullptr;
+    uint32_t* const mqs = (HAS_Q && split == 1) ? it.dtok : nullptr;
+    uint32_t* const Mq = HAS_Q ? it.Mq : nullptr;
+    if (MI355_SWZ_BANKS && __builtin_amdgcn_readfirstlane((int)it.B[(size_t)e * BSTRIDE + WINDOW_SIZE + 2]))
+        m3_epoch<HAS_Q, true, SINGLE>(s_T, s_next, e, part, it.in, it.n, it.S, it.B, it.M, Mq, checks, checks_q, aligned16, sg,
+                                      batch_no_override(), split, ms, mqs, &it.st->sort_bad);
+    else
+        m3_epoch<HAS_Q, false, SINGLE>(s_T, s_next, e, part, it.in, it.n, it.S, it.B, it.M, Mq, checks, checks_q, aligned16, sg,
+                                       batch_no_override(), split, ms, mqs, &it.st->sort_bad);
+}
+
+__global__ __launch_bounds__(256) void kb_adv(BatchArgs bat_, ParseCfg cfg) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_ADV, local, count)];
+    k_adv_body(local, it.n, it.M, cfg.use_quarter ? it.Mq : nullptr, cfg, it.adv, SegEnds{it.seg_ends, 1u}, 0u);
+}
+
+// k_emit<1, STEPS>: the names the body reads, from the descriptor
+template <bool STEPS>
+__global__ __launch_bounds__(256) void kb_emit(BatchArgs bat_, ParseCfg cfg) {
+    constexpr int MODE = 1;
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_EMIT, local, count)];
+    const uint8_t* in = it.in;
+    uint32_t n = it.n, K = it.K0;
+    const uint32_t* M = it.M;
+    const uint32_t* Mq = cfg.use_quarter ? it.Mq : nullptr;
+    const uint16_t* adv = STEPS ? nullptr : it.adv;
+    uint32_t *E0 = it.E0, *tokbuf = it.tokbuf, *cnt = it.cnt, *Xs = it.xs;
+    uint32_t pos0 = 0, n_total = it.n, runup0 = 0, seg0 = 0;
+    SegEnds sg{it.seg_ends, 1u};
+    SpecFix fix{it.fixlist, it.badmap, &it.st->sc.n_fix[0]};
+#define BX_ local
+#include "body_k_emit.inc"
+#undef BX_
+}
+
+template <bool STEPS>
+__global__ __launch_bounds__(SMALL_FIX_T) void kb_small_fix(BatchArgs bat_, ParseCfg cfg) {
+    const BatchItem& it = bat_.it[blockIdx.x];
+    k_small_fix_body<STEPS>(0u, it.in, it.n, it.K0, it.M, cfg.use_quarter ? it.Mq : nullptr, cfg, STEPS ? nullptr : it.adv, it.E0,
+                            it.tokbuf, it.cnt, SegEnds{it.seg_ends, 1u}, it.xs, it.badmap, it.fixlist, it.nb_max, 0u, &it.st->spec_bad,
+                            it.base, &it.st->sc, it.tend, it.pb, it.bstart, it.q13, it.tab, it.q1_check);
+}
+
+__global__ __launch_bounds__(256) void kb_compact(BatchArgs bat_) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_COMPACT, local, count)];
+    k_compact_body(local, it.K0, it.tokbuf, it.cnt, it.base, it.dtok, &it.st->sc, 0u);
+}
+
+template <uint32_t HT>
+__global__ __launch_bounds__(HT) void kb_block_hist(BatchArgs bat_) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_HIST, local, count)];
+    k_block_hist_body<HT>(local, count, it.dtok, &it.st->sc, it.ll_freq, it.d_freq, it.tab, 0u, reinterpret_cast<uint32_t*>(it.out),
+                          it.out_words);
+}
+
+__global__ __launch_bounds__(128) void kb_block_header(BatchArgs bat_) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_HEADER, local, count)];
+    k_block_header_body(local, &it.st->sc, it.ll_freq, it.d_freq, it.hdr, 0u);
+}
+
+__global__ __launch_bounds__(1024) void kb_plan(BatchArgs bat_, uint64_t bit_base, uint32_t compat) {
+    __shared__ uint32_t s_red[16], s_flag[3];
+    const BatchItem& it = bat_.it[blockIdx.x];
+    plan_blocks(s_red, s_flag, &it.st->sc, it.hdr, it.bstart, it.q13, it.plan, bit_base, compat, it.tab.sync,
+                reinterpret_cast<uint32_t*>(it.out), Piece{0u, 0u, 1u});
+}
+
+template <uint32_t PKT>
+__global__ __launch_bounds__(PKT) void kb_pack(BatchArgs bat_, uint32_t compat) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_PACK, local, count)];
+    const uint8_t* in = it.in;
+    uint32_t n = it.n, piece = 0;
+    const uint32_t* dtok = it.dtok;
+    const DevScalars* sc = &it.st->sc;
+    const BlockHeader* hdr = it.hdr;
+    const BlockPlan* plan = it.plan;
+    const uint32_t *bstart = it.bstart, *q13 = it.q13, *ll_freq = it.ll_freq, *d_freq = it.d_freq;
+    uint32_t* out32 = reinterpret_cast<uint32_t*>(it.out);
+    BlockTab tab = it.tab;
+#define BX_ local
+#include "body_k_pack.inc"
+#undef BX_
+}
+
+__global__ __launch_bounds__(256) void kb_adler_part(BatchArgs bat_) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_ADLER, local, count)];
+    const uint8_t* in = it.in;
+    uint32_t n = it.n;
+    DevScalars* sc = &it.st->sc;
+#define BX_ local
+#include "body_k_adler_part.inc"
+#undef BX_
+}
+
+// k_adler_fold and k_zlib_frame of an item, one after the other in one lane
+__global__ __launch_bounds__(64) void kb_zlib_tail(BatchArgs bat_) {
+    const BatchItem& it = bat_.it[blockIdx.x];
+    k_adler_fold_body(0u, it.n, &it.st->sc);
+    k_zlib_frame_body(0u, &it.st->sc, it.out, 1u);
+}
+
+}  // namespace mi355
+
+namespace {
+
+constexpr uint32_t BATCH_ITEMS_MAX = 65536;  // items of one launch set (the descriptors and running sums: 38 MiB at most)
+
+// one item of a batch as the launch sets see it: device buffers
+struct BatchView {
+    const uint8_t* d_in;
+    uint64_t n;
+    uint8_t* d_out;
+    size_t need;
+    size_t idx;  // in the caller's array
+};
+
+// Can the batched kernels take this item?  (Else: the one-input path, after the launch sets.)
+bool batch_takes(const ParseCfg& cfg, uint64_t n) {
+    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
+    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
+    return MI355_SMALL_TAIL && hashing && !(cfg.use_quarter && cq == 0) && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
+}
+
+enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
+
+// One launch set over v[0..k): the kernels, one copy of the items' scalars back, one wait.  out_len / outcome per item.
+int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const mi355_deflate_opts* o, const ParseCfg& cfg,
+                     hipStream_t st, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
+    const bool zlib = o->wrapper == 1;
+    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
+    const bool has_q = cfg.use_quarter && cq;
+    // the items' workspaces, one behind the other in the context's one workspace
+    std::vector<uint64_t> ws_off(k + 1, 0);
+    for (uint32_t i = 0; i < k; i++) ws_off[i + 1] = ws_off[i] + carve(nullptr, v[i].n, cfg.use_quarter).bytes;
+    int rc = ensure_ws(c, ws_off[k]);
+    if (rc) return rc;
+    const size_t pre_words = (size_t)BS_N * (k + 1);
+    const size_t desc_bytes = align_up(sizeof(BatchItem) * k + sizeof(uint32_t) * pre_words, 256);
+    const size_t state_bytes = sizeof(DevState) * k;
+    rc = ensure_buf(c, &c->b_dev, &c->b_dev_cap, desc_bytes + state_bytes);
+    if (rc) return rc;
+    if (desc_bytes + state_bytes > c->b_host_cap) {
+        if (c->b_host) (void)hipHostFree(c->b_host);
+        c->b_host = nullptr;
+        c->b_host_cap = 0;
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->b_host), desc_bytes + state_bytes, 0));
+        c->b_host_cap = desc_bytes + state_bytes;
+    }
+    BatchItem* hit = reinterpret_cast<BatchItem*>(c->b_host);
+    uint32_t* hpre = reinterpret_cast<uint32_t*>(c->b_host + sizeof(BatchItem) * k);
+    DevState* hst = reinterpret_cast<DevState*>(c->b_host + desc_bytes);
+    DevState* dst = reinterpret_cast<DevState*>(c->b_dev + desc_bytes);
+    // the walk's parts per epoch: as launch_walk cuts the epochs of one call, for all epochs of the set
+    uint64_t epochs = 0;
+    for (uint32_t i = 0; i < k; i++) epochs += (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
+    const uint32_t cus = c->n_cu ? c->n_cu : 256u;
+    uint32_t split = match3_split(epochs, c->n_cu);
+    const bool single = split >= MI355_M3_SPLIT_MAX && epochs * split * 2 <= cus;
+    if (single) split *= 2;
+    for (uint32_t s = 0; s < BS_N; s++) hpre[(size_t)s * (k + 1)] = 0;
+    for (uint32_t i = 0; i < k; i++) {
+        const Workspace w = carve(c->ws + ws_off[i], v[i].n, cfg.use_quarter);
+        BatchItem& d = hit[i];
+        memset(&d, 0, sizeof d);
+        d.in = v[i].d_in;
+        d.n = (uint32_t)v[i].n;
+        d.K0 = w.K0;
+        d.nb_max = w.nb_max;
+        d.q1_check = v[i].n >= MAX_BUFFER_LENGTH ? 1u : 0u;
+        d.out_words = (uint32_t)(v[i].need / 4);
+        d.M = w.M;
+        d.Mq = w.Mq;
+        d.adv = w.adv;
+        d.S = w.sorted + WINDOW_SIZE;
+        d.B = w.buckets;
+        d.E0 = w.levels[0].E;
+        d.tokbuf = w.tokbuf;
+        d.cnt = w.cnt;
+        d.xs = w.xs;
+        d.badmap = w.badmap;
+        d.fixlist = w.fixlist;
+        d.base = w.base;
+        d.tend = w.tend;
+        d.pb = w.pb;
+        d.bstart = w.bstart;
+        d.q13 = w.q13;
+        d.dtok = w.dtok;
+        d.ll_freq = w.ll_freq;
+        d.d_freq = w.d_freq;
+        d.seg_ends = w.seg_ends;
+        d.tab = w.tab;
+        d.hdr = w.hdr;
+        d.plan = w.plan;
+        d.st = dst + i;
+        d.out = v[i].d_out;
+        const uint64_t n_ep = (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
+        const uint64_t wg[BS_N] = {n_ep, n_ep * split, cdiv(v[i].n, ADV_TILE), cdiv(w.K0, 4), cdiv(w.K0, 4), (uint64_t)w.nb_max * PSPLIT,
+                                   w.nb_max, (uint64_t)w.nb_max * PSPLIT, cdiv(v[i].n, ADLER_CHUNK)};
+        for (uint32_t s = 0; s < BS_N; s++) {
+            const uint64_t t = (uint64_t)hpre[(size_t)s * (k + 1) + i] + wg[s];
+            if (t > 0x7fffffffull) return MI355_E_ARG;  // (a launch set of at most 256 MiB of input is far below this)
+            hpre[(size_t)s * (k + 1) + i + 1] = (uint32_t)t;
+        }
+    }
+    auto total = [&](uint32_t s) { return hpre[(size_t)s * (k + 1) + k]; };
+    const BatchArgs a{reinterpret_cast<const BatchItem*>(c->b_dev), reinterpret_cast<const uint32_t*>(c->b_dev + sizeof(BatchItem) * k), k};
+    HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, sizeof(BatchItem) * k + sizeof(uint32_t) * pre_words, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(dst, 0, state_bytes, st));  // (the flags behind the scalars: k_sort clears the scalars themselves)
+    // ---- match table ----
+    if (c->sort_mode == 1)
+        hipLaunchKernelGGL(kb_sort<1>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, c->sort_break ? 3u : 1u);
+    else
+        hipLaunchKernelGGL(kb_sort<0>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, 1u);
+#define MI355_BWALK(Q, SNG) hipLaunchKernelGGL((kb_walk<Q, SNG>), dim3(total(BS_WALK)), dim3(M3T), 0, st, a, cfg.checks, Q ? cq : 0u, split)
+    if (has_q && single)
+        MI355_BWALK(true, true);
+    else if (has_q)
+        MI355_BWALK(true, false);
+    else if (single)
+        MI355_BWALK(false, true);
+    else
+        MI355_BWALK(false, false);
+#undef MI355_BWALK
+    // ---- parse: speculative segment entries, the check and repair, the block table (k_small_fix), compaction ----
+    const bool in_emit = steps_in_emit(c, cfg, 1);
+    if (!in_emit) hipLaunchKernelGGL(kb_adv, dim3(total(BS_ADV)), dim3(256), 0, st, a, cfg);
+    if (in_emit) {
+        hipLaunchKernelGGL(kb_emit<true>, dim3(total(BS_EMIT)), dim3(256), 0, st, a, cfg);
+        hipLaunchKernelGGL(kb_small_fix<true>, dim3(k), dim3(SMALL_FIX_T), 0, st, a, cfg);
+    } else {
+        hipLaunchKernelGGL(kb_emit<false>, dim3(total(BS_EMIT)), dim3(256), 0, st, a, cfg);
+        hipLaunchKernelGGL(kb_small_fix<false>, dim3(k), dim3(SMALL_FIX_T), 0, st, a, cfg);
+    }
+    hipLaunchKernelGGL(kb_compact, dim3(total(BS_COMPACT)), dim3(256), 0, st, a);
+    // ---- blocks ----
+    if (total(BS_HIST) <= cus)
+        hipLaunchKernelGGL(kb_block_hist<1024>, dim3(total(BS_HIST)), dim3(1024), 0, st, a);
+    else
+        hipLaunchKernelGGL(kb_block_hist<256>, dim3(total(BS_HIST)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(kb_block_header, dim3(total(BS_HEADER)), dim3(128), 0, st, a);
+    hipLaunchKernelGGL(kb_plan, dim3(k), dim3(1024), 0, st, a, (uint64_t)(zlib ? 16 : 0), (uint32_t)o->compat);
+    if (total(BS_PACK) <= cus)
+        hipLaunchKernelGGL(kb_pack<PKT_SMALL>, dim3(total(BS_PACK)), dim3(PKT_SMALL), 0, st, a, (uint32_t)o->compat);
+    else
+        hipLaunchKernelGGL(kb_pack<PKT_LARGE>, dim3(total(BS_PACK)), dim3(PKT_LARGE), 0, st, a, (uint32_t)o->compat);
+    if (zlib) {
+        hipLaunchKernelGGL(kb_adler_part, dim3(total(BS_ADLER)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(kb_zlib_tail, dim3(k), dim3(64), 0, st, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hst, dst, state_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    bool sort_bad = false;
+    for (uint32_t i = 0; i < k; i++) sort_bad |= hst[i].sort_bad != 0;
+    if (sort_bad) {  // (never seen on MI355X; the set is done again with ballot ranks, as run_encode does)
+        if (c->sort_mode == 0) {
+            c->err = "batched walk: a bucket out of order with ballot ranks";
+            return MI355_E_HIP;
+        }
+        c->sort_mode = 0;
+        c->lds_order_ok = false;
+        c->sort_break = 0;
+        return batch_launch_set(c, v, k, o, cfg, st, out_len, outcome, sums);
+    }
+    for (uint32_t i = 0; i < k; i++) {
+        const DevScalars& s = hst[i].sc;
+        uint64_t wpos = 0;
+        out_len[i] = 0;
+        if (hst[i].spec_bad)
+            outcome[i] = BO_SPEC;
+        else if (hit[i].q1_check && s.b0_full && q1_rewarm(s.b0_last_tok, s.b0_last_pos, cfg.mode, v[i].n, &wpos))
+            outcome[i] = BO_Q1;
+        else if (s.ref_panic)
+            outcome[i] = BO_PANIC;
+        else {
+            outcome[i] = BO_OK;
+            out_len[i] = (size_t)((s.total_bits + 7) / 8) + (zlib ? 6 : 0);
+            sums->T += s.T;
+            sums->nb += s.nb;
+            sums->n_stored += s.n_stored;
+            sums->n_fixed += s.n_fixed;
+            sums->n_dynamic += s.n_dynamic;
+            sums->q13_hits += s.q13_hits;
+        }
+    }
+    return MI355_OK;
+}
+
+// The whole batch: launch sets over the items the batched kernels take, then the others one by one through the one-input path.
+// host: the items' buffers are the caller's host memory (gathered into the context's device staging per launch set).
+int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, hipStream_t st, bool host,
+              void* hip_stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (c->live_shard) {
+        c->err = "this context holds a sharded encode between mi355_shard_begin and mi355_shard_end";
+        return MI355_E_STATE;
+    }
+    ParseCfg cfg;
+    cfg.checks = o->max_hash_checks;
+    cfg.lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;
+    cfg.mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);
+    cfg.use_quarter = (cfg.mode == MODE_LAZY && cfg.lazy_lt > 32) ? 1 : 0;
+    if (cfg.mode == MODE_LAZY && cfg.lazy_lt < 3) {
+        c->err = "lazy_if_less_than < 3 with Lazy matching is not supported (SURVEY A.4 Q3)";
+        return MI355_E_UNSUPPORTED;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->last_plan = nullptr;  // (the workspace is carved again below)
+    c->last_nb = 0;
+    mi355_batch_info bi;
+    memset(&bi, 0, sizeof bi);
+    bi.n_items = n_items;
+    DevScalars sums;
+    memset(&sums, 0, sizeof sums);
+    uint64_t sum_out = 0;
+    std::vector<size_t> singles;
+    std::vector<uint8_t> single_q1(n_items, 0), single_spec(n_items, 0);
+    std::vector<BatchView> v;
+    for (size_t i = 0; i < n_items; i++) {
+        mi355_batch_item& it = items[i];
+        bi.in_len += it.in_len;
+        const size_t need = mi355_deflate_bound_ex(it.in_len, o->wrapper, 0, 0);
+        it.out_len = 0;
+        it.status = MI355_OK;
+        if (it.out_cap < need) {
+            it.out_len = need;
+            it.status = MI355_E_OUT_TOO_SMALL;
+        } else if (batch_takes(cfg, it.in_len)) {
+            v.push_back(BatchView{reinterpret_cast<const uint8_t*>(it.in), it.in_len, reinterpret_cast<uint8_t*>(it.out), need, i});
+        } else {
+            singles.push_back(i);
+        }
+    }
+    // ---- launch sets: consecutive items up to c->batch_bytes of input (at least one) ----
+    std::vector<size_t> out_len;
+    std::vector<BatchOutcome> outcome;
+    for (size_t s0 = 0; s0 < v.size();) {
+        size_t s1 = s0 + 1;
+        uint64_t bytes = v[s0].n;
+        while (s1 < v.size() && s1 - s0 < BATCH_ITEMS_MAX && bytes + v[s1].n <= c->batch_bytes) bytes += v[s1++].n;
+        const uint32_t k = (uint32_t)(s1 - s0);
+        BatchView* sv = v.data() + s0;
+        std::vector<BatchView> staged;
+        if (host) {  // the inputs into the device staging, 256-byte aligned each; the outputs behind them the same way
+            std::vector<size_t> in_off(k + 1, 0), out_off(k + 1, 0);
+            for (uint32_t i = 0; i < k; i++) {
+                in_off[i + 1] = in_off[i] + align_up(sv[i].n + 64, 256);
+                out_off[i + 1] = out_off[i] + align_up(sv[i].need, 256);
+            }
+            int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, in_off[k]);
+            if (rc) return rc;
+            rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_off[k]);
+            if (rc) return rc;
+            staged.assign(sv, sv + k);
+            for (uint32_t i = 0; i < k; i++) {
+                HIPCHK(c, hipMemcpyAsync(c->d_in + in_off[i], sv[i].d_in, sv[i].n, hipMemcpyHostToDevice, st));
+                staged[i].d_in = c->d_in + in_off[i];
+                staged[i].d_out = c->d_out + out_off[i];
+            }
+            sv = staged.data();
+        }
+        out_len.assign(k, 0);
+        outcome.assign(k, BO_OK);
+        const int rc = batch_launch_set(c, sv, k, o, cfg, st, out_len.data(), outcome.data(), &sums);
+        if (rc) return rc;
+        bi.sub_batches++;
+        for (uint32_t i = 0; i < k; i++) {
+            mi355_batch_item& it = items[sv[i].idx];
+            switch (outcome[i]) {
+            case BO_OK:
+                it.out_len = out_len[i];
+                sum_out += out_len[i];
+                bi.n_batched++;
+                if (host) HIPCHK(c, hipMemcpyAsync(it.out, sv[i].d_out, out_len[i], hipMemcpyDeviceToHost, st));
+                break;
+            case BO_PANIC:
+                it.status = MI355_E_REF_PANIC;
+                bi.n_batched++;
+                break;
+            case BO_Q1:
+                single_q1[sv[i].idx] = 1;
+                singles.push_back(sv[i].idx);
+                break;
+            case BO_SPEC:
+                single_spec[sv[i].idx] = 1;
+                singles.push_back(sv[i].idx);
+                break;
+            }
+        }
+        if (host) HIPCHK(c, hipStreamSynchronize(st));
+        s0 = s1;
+    }
+    // ---- the rest, one by one, exactly as the one-input entries do it ----
+    std::sort(singles.begin(), singles.end());
+    uint32_t q1_any = 0, spec_any = 0;
+    for (size_t i : singles) {
+        mi355_batch_item& it = items[i];
+        size_t len = 0;
+        int rc;
+        if (host)
+            rc = mi355_deflate_encode(c, reinterpret_cast<const uint8_t*>(it.in), it.in_len, o, reinterpret_cast<uint8_t*>(it.out),
+                                      it.out_cap, &len);
+        else
+            rc = mi355_deflate_encode_device(c, it.in, it.in_len, o, it.out, it.out_cap, &len, hip_stream);
+        if (rc == MI355_E_HIP) return rc;  // (the device or the runtime failed: nothing else is trustworthy)
+        bi.n_single++;
+        bi.n_q1_single += single_q1[i];
+        bi.n_spec_single += single_spec[i];
+        it.status = rc;
+        it.out_len = (rc == MI355_OK || rc == MI355_E_OUT_TOO_SMALL) ? len : 0;
+        if (rc == MI355_OK) {
+            sum_out += len;
+            const mi355_deflate_info& in1 = c->info;
+            sums.T += (uint32_t)in1.n_tokens;
+            sums.nb += in1.n_blocks;
+            sums.n_stored += in1.n_stored;
+            sums.n_fixed += in1.n_fixed;
+            sums.n_dynamic += in1.n_dynamic;
+            sums.q13_hits += in1.q13_hits;
+            q1_any |= in1.q1_rewarm;
+            spec_any |= in1.spec_fallback;
+        }
+    }
+    if (!host) HIPCHK(c, hipStreamSynchronize(st));
+    bi.out_len = sum_out;
+    bi.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->batch = bi;
+    // mi355_deflate_last_info: the batch as a whole; mi355_deflate_last_blocks: none
+    mi355_deflate_info& info = c->info;
+    memset(&info, 0, sizeof info);
+    info.in_len = bi.in_len;
+    info.out_len = bi.out_len;
+    info.n_tokens = sums.T;
+    info.n_blocks = sums.nb;
+    info.n_stored = sums.n_stored;
+    info.n_fixed = sums.n_fixed;
+    info.n_dynamic = sums.n_dynamic;
+    info.q13_hits = sums.q13_hits;
+    info.q1_rewarm = q1_any ? 1u : 0u;
+    info.spec_fallback = spec_any;
+    info.passes = 1;
+    info.total_ms = bi.total_ms;
+    c->pend_passes = 0;
+    c->last_plan = nullptr;
+    c->last_nb = 0;
+    for (size_t i = 0; i < n_items; i++)
+        if (items[i].status != MI355_OK) return items[i].status;
+    return MI355_OK;
+}
+
+// the checks of the call itself (nothing is written to an item when one fails)
+int batch_args_ok(mi355_deflate_ctx* c, const mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, bool device) {
+    if (!o || (!items && n_items)) return MI355_E_ARG;
+    if (o->wrapper > 1) {
+        c->err = "batched encode: wrapper 0 (raw) or 1 (zlib) only";
+        return MI355_E_ARG;
+    }
+    if (o->flush != MI355_FLUSH_FINISH) {
+        c->err = "batched encode: MI355_FLUSH_FINISH only";
+        return MI355_E_ARG;
+    }
+    for (size_t i = 0; i < n_items; i++) {
+        if ((!items[i].in && items[i].in_len) || !items[i].out) return MI355_E_ARG;
+        if (device && (reinterpret_cast<uintptr_t>(items[i].out) & 3)) {
+            c->err = "batched encode: every item's device output must be 4-byte aligned";
+            return MI355_E_ARG;
+        }
+    }
+    return MI355_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355_deflate_encode_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    int rc = batch_args_ok(c, items, n_items, opts, false);
+    if (rc) return rc;
+    return run_batch(c, items, n_items, opts, c->own_stream, true, nullptr);
+}
+
+int mi355_deflate_encode_batch_device(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
+                                      void* hip_stream) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    int rc = batch_args_ok(c, items, n_items, opts, true);
+    if (rc) return rc;
+    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    return run_batch(c, items, n_items, opts, st, false, hip_stream);
+}
+
+int mi355_deflate_last_batch_info(mi355_deflate_ctx* c, mi355_batch_info* info) {
+    if (!c || !info) return MI355_E_ARG;
+    *info = c->batch;
+    return MI355_OK;
+}
+
+}  // extern "C"

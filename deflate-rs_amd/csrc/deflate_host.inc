@@ -219,6 +219,13 @@ struct mi355_deflate_ctx {
     struct mi355_shard* shard_cache = nullptr;  // deflate_shard.inc: the shard object of the last sharded encode
     struct mi355_shard* live_shard = nullptr;   // a shard between _begin and _end: its tokens and tables live in the workspace,
                                                 // so no other encode may run on this context meanwhile (MI355_E_STATE)
+    // deflate_batch.inc: the descriptors and running sums of a launch set and the items' scalars (device; page-locked staging)
+    uint8_t* b_dev = nullptr;
+    size_t b_dev_cap = 0;
+    uint8_t* b_host = nullptr;
+    size_t b_host_cap = 0;
+    uint64_t batch_bytes = 256ull << 20;  // MI355_CFG_BATCH_BYTES: input bytes of one launch set
+    mi355_batch_info batch = {};          // mi355_deflate_last_batch_info
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1640,6 +1647,8 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->out_stream) (void)hipStreamDestroy(c->out_stream);
     if (c->blk_stream) (void)hipStreamDestroy(c->blk_stream);
     if (c->h_piece) (void)hipHostFree(c->h_piece);
+    if (c->b_dev) (void)hipFree(c->b_dev);
+    if (c->b_host) (void)hipHostFree(c->b_host);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

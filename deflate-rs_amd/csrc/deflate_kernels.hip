@@ -790,8 +790,8 @@ struct SortInit {
     uint32_t seg_val;
 };
 template <int MODE>
-__global__ __launch_bounds__(1024) void k_sort(const uint8_t* __restrict__ in, uint32_t n, HashOverride ov,
-                                               uint16_t* __restrict__ Sg, uint16_t* __restrict__ Bg, uint32_t e0, uint32_t dbl,
+__device__ __forceinline__ void k_sort_body(uint32_t bx_, const uint8_t* in, uint32_t n, HashOverride ov,
+                                               uint16_t* Sg, uint16_t* Bg, uint32_t e0, uint32_t dbl,
                                                SortInit init) {
     __shared__ __attribute__((aligned(16))) uint16_t sH[WINDOW_SIZE];  // hashes; the sorted array at the end
     __shared__ __attribute__((aligned(16))) uint32_t sBuf[WINDOW_SIZE / 2];  // histogram (u16 pairs), then pass-1 output (u16) / cursors
@@ -800,11 +800,11 @@ __global__ __launch_bounds__(1024) void k_sort(const uint8_t* __restrict__ in, u
     __shared__ uint32_t s_runs;  // pieces of 512 positions that lie in a run of one byte
     const uint32_t tid = threadIdx.x;
     if (tid == 0) s_runs = 0;
-    if (init.sc && blockIdx.x == 0) {
+    if (init.sc && bx_ == 0) {
         for (uint32_t i = tid; i < init.sc_words; i += 1024) init.sc[i] = 0;
         if (tid == 0 && init.seg_end) *init.seg_end = init.seg_val;
     }
-    const uint32_t e = e0 + blockIdx.x;
+    const uint32_t e = e0 + bx_;
     const uint64_t E = (uint64_t)e * WINDOW_SIZE;
     const uint32_t J = epoch_active(n, E);
     unsigned long long ks_t = __builtin_readcyclecounter();
@@ -991,6 +991,12 @@ __global__ __launch_bounds__(1024) void k_sort(const uint8_t* __restrict__ in, u
         const uint4 v = fin[k];
         out[k] = make_uint4(v.x << dbl, v.y << dbl, v.z << dbl, v.w << dbl);
     }
+}
+template <int MODE>
+__global__ __launch_bounds__(1024) void k_sort(const uint8_t* __restrict__ in, uint32_t n, HashOverride ov,
+                                               uint16_t* __restrict__ Sg, uint16_t* __restrict__ Bg, uint32_t e0, uint32_t dbl,
+                                               SortInit init) {
+    k_sort_body<MODE>(blockIdx.x, in, n, ov, Sg, Bg, e0, dbl, init);
 }
 
 #ifdef MI355_MATCH_STATS
@@ -1745,10 +1751,10 @@ __global__ __launch_bounds__(256) void k_rle(const uint8_t* __restrict__ in, uin
 // deferral needs a strictly longer match (3 .. 258), so a step reads at most 256 entries beyond its position -- no step
 // leaves the tile, the reads are plain LDS reads at 32-bit tile-relative positions (with a 64-entry halo and a fall-back
 // to global memory they were generic loads behind 64-bit selects, and the kernel was bound by its vector instructions).
-__global__ __launch_bounds__(256) void k_adv(uint32_t n, const uint32_t* __restrict__ M, const uint32_t* __restrict__ Mq,
-                                             ParseCfg cfg, uint16_t* __restrict__ adv, SegEnds sg, uint32_t blk0) {
+__device__ __forceinline__ void k_adv_body(uint32_t bx_, uint32_t n, const uint32_t* M, const uint32_t* Mq,
+                                             ParseCfg cfg, uint16_t* adv, SegEnds sg, uint32_t blk0) {
     __shared__ __attribute__((aligned(16))) uint32_t sM[ADV_TILE + ADV_HALO], sQ[ADV_TILE + ADV_HALO];
-    const uint64_t t0 = ((uint64_t)blockIdx.x + blk0) * ADV_TILE;  // (blk0: a launch may cover a range of tiles)
+    const uint64_t t0 = ((uint64_t)bx_ + blk0) * ADV_TILE;  // (blk0: a launch may cover a range of tiles)
     const bool useq = Mq != nullptr;
     // (the tables are padded by 64 entries and 256-byte aligned, a tile starts at a multiple of 1024 entries:
     // sixteen bytes per lane; entries beyond the padding read as "no match")
@@ -1826,6 +1832,10 @@ __global__ __launch_bounds__(256) void k_adv(uint32_t n, const uint32_t* __restr
     } else {
         for (uint32_t q = 0; q < 4 && r0 + q < left; q++) adv[t0 + r0 + q] = a[q];
     }
+}
+__global__ __launch_bounds__(256) void k_adv(uint32_t n, const uint32_t* __restrict__ M, const uint32_t* __restrict__ Mq,
+                                             ParseCfg cfg, uint16_t* __restrict__ adv, SegEnds sg, uint32_t blk0) {
+    k_adv_body(blockIdx.x, n, M, Mq, cfg, adv, sg, blk0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2094,33 +2104,9 @@ __global__ __launch_bounds__(256) void k_emit(const uint8_t* __restrict__ in, ui
                                               uint32_t* __restrict__ E0, uint32_t* __restrict__ tokbuf,
                                               uint32_t* __restrict__ cnt, uint32_t pos0, uint32_t n_total, SegEnds sg,
                                               uint32_t* __restrict__ Xs, SpecFix fix, uint32_t runup0, uint32_t seg0) {
-    constexpr uint32_t ROW = EmitRows<MODE, STEPS>::ROW;
-    __shared__ __attribute__((aligned(8))) uint16_t s_adv[4][ROW];
-    __shared__ __attribute__((aligned(8))) uint16_t s_pp[4][ROW];
-    __shared__ uint32_t s_np[4], s_exit[4];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint64_t k = (uint64_t)blockIdx.x * 4 + wv + seg0;  // (seg0: a launch may cover a range of segments)
-    uint32_t given = 0;  // MODE 2: the entry the segment is parsed from
-    if (MODE == 2) {
-        const uint32_t nf = *fix.n;
-        if (nf > FIX_MAX || k >= nf) return;
-        // (the exit of the segment before it as k_spec_check saw it -- not Xs[k - 1] as it is now, which a wave that repairs the
-        // segments before this one may be rewriting: what a repair is based on must not depend on which wave runs first)
-        given = fix.list[2 * k + 1];
-        k = fix.list[2 * k];
-    }
-    if (k >= K) return;  // whole wave; no workgroup barrier is used below
-    constexpr bool SPEC = MODE == 1;
-    constexpr uint32_t REG = EmitRows<MODE, STEPS>::REG;
-    uint16_t* A = s_adv[wv];
-    uint16_t* P = s_pp[wv];
-#define EMIT_NP s_np[wv]
-#define EMIT_EXIT s_exit[wv]
-#define EMIT_BADMAP fix.badmap
-#include "emit_body.inc"
-#undef EMIT_NP
-#undef EMIT_EXIT
-#undef EMIT_BADMAP
+#define BX_ blockIdx.x
+#include "body_k_emit.inc"
+#undef BX_
 }
 
 // Quirk Q1 (lz77.rs:628-638): block 0 holds 31744 tokens and its last token -- tk, at tp < WINDOW_SIZE -- leaves the encoder inside
@@ -2263,10 +2249,10 @@ __global__ void k_scan_zero(DevScalars* sc) {
 }
 
 // k_compact: tokens of all segments into one dense stream.
-__global__ __launch_bounds__(256) void k_compact(uint32_t K, const uint32_t* __restrict__ tokbuf,
-                                                 const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
-                                                 uint32_t* __restrict__ dtok, const DevScalars* sc, uint32_t seg0) {
-    uint64_t k = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6) + seg0;
+__device__ __forceinline__ void k_compact_body(uint32_t bx_, uint32_t K, const uint32_t* tokbuf,
+                                                 const uint32_t* cnt, const uint32_t* base,
+                                                 uint32_t* dtok, const DevScalars* sc, uint32_t seg0) {
+    uint64_t k = (uint64_t)bx_ * 4 + (threadIdx.x >> 6) + seg0;
     if (k >= K || spec_failed(sc)) return;
     uint32_t lane = threadIdx.x & 63;
     uint32_t c = cnt[k], b = base[k];
@@ -2276,6 +2262,11 @@ __global__ __launch_bounds__(256) void k_compact(uint32_t K, const uint32_t* __r
     const uint32_t c4 = c & ~3u;
     for (uint32_t i = 4 * lane; i < c4; i += 256) *reinterpret_cast<uint4*>(dtok + b + i) = *reinterpret_cast<const uint4*>(src + i);
     if (lane < (c & 3u)) dtok[b + c4 + lane] = src[c4 + lane];
+}
+__global__ __launch_bounds__(256) void k_compact(uint32_t K, const uint32_t* __restrict__ tokbuf,
+                                                 const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
+                                                 uint32_t* __restrict__ dtok, const DevScalars* sc, uint32_t seg0) {
+    k_compact_body(blockIdx.x, K, tokbuf, cnt, base, dtok, sc, seg0);
 }
 
 // start position of token t (t < T); the whole wave calls it.  The segment that holds the token -- the last k with
@@ -2448,14 +2439,14 @@ __global__ __launch_bounds__(256) void k_block_bounds(uint32_t n, uint32_t K, ui
 #endif
 constexpr uint32_t SMALL_TAIL_SEGS = MI355_SMALL_SEGS, SMALL_FIX_T = 512, SMALL_FIX_PER = SMALL_TAIL_SEGS / SMALL_FIX_T;  // (2 MiB; segments a thread scans)
 template <bool STEPS>
-__global__ __launch_bounds__(SMALL_FIX_T) void k_small_fix(const uint8_t* __restrict__ in, uint32_t n, uint32_t K,
-                                                           const uint32_t* __restrict__ M, const uint32_t* __restrict__ Mq, ParseCfg cfg,
-                                                           const uint16_t* __restrict__ adv, uint32_t* E0, uint32_t* __restrict__ tokbuf,
+__device__ __forceinline__ void k_small_fix_body(uint32_t bx_, const uint8_t* in, uint32_t n, uint32_t K,
+                                                           const uint32_t* M, const uint32_t* Mq, ParseCfg cfg,
+                                                           const uint16_t* adv, uint32_t* E0, uint32_t* tokbuf,
                                                            uint32_t* cnt, SegEnds sg, uint32_t* Xs, uint32_t* badmap, uint32_t* list,
-                                                           uint32_t nb_max, uint32_t sync_final, uint32_t* __restrict__ spec_bad,
-                                                           uint32_t* __restrict__ base, DevScalars* sc, uint32_t* __restrict__ tend,
-                                                           uint32_t* __restrict__ pb, uint32_t* __restrict__ bstart,
-                                                           uint32_t* __restrict__ q13, BlockTab tab, uint32_t q1_cancel) {
+                                                           uint32_t nb_max, uint32_t sync_final, uint32_t* spec_bad,
+                                                           uint32_t* base, DevScalars* sc, uint32_t* tend,
+                                                           uint32_t* pb, uint32_t* bstart,
+                                                           uint32_t* q13, BlockTab tab, uint32_t q1_cancel) {
     constexpr uint32_t ROW = EmitRows<2, STEPS>::ROW, NW = SMALL_FIX_T / 64;
     __shared__ __attribute__((aligned(8))) uint16_t s_adv[NW][ROW];
     __shared__ __attribute__((aligned(8))) uint16_t s_pp[NW][ROW];
@@ -2592,6 +2583,17 @@ __global__ __launch_bounds__(SMALL_FIX_T) void k_small_fix(const uint8_t* __rest
         }
     }
 }
+template <bool STEPS>
+__global__ __launch_bounds__(SMALL_FIX_T) void k_small_fix(const uint8_t* __restrict__ in, uint32_t n, uint32_t K,
+                                                           const uint32_t* __restrict__ M, const uint32_t* __restrict__ Mq, ParseCfg cfg,
+                                                           const uint16_t* __restrict__ adv, uint32_t* E0, uint32_t* __restrict__ tokbuf,
+                                                           uint32_t* cnt, SegEnds sg, uint32_t* Xs, uint32_t* badmap, uint32_t* list,
+                                                           uint32_t nb_max, uint32_t sync_final, uint32_t* __restrict__ spec_bad,
+                                                           uint32_t* __restrict__ base, DevScalars* sc, uint32_t* __restrict__ tend,
+                                                           uint32_t* __restrict__ pb, uint32_t* __restrict__ bstart,
+                                                           uint32_t* __restrict__ q13, BlockTab tab, uint32_t q1_cancel) {
+    k_small_fix_body<STEPS>(blockIdx.x, in, n, K, M, Mq, cfg, adv, E0, tokbuf, cnt, sg, Xs, badmap, list, nb_max, sync_final, spec_bad, base, sc, tend, pb, bstart, q13, tab, q1_cancel);
+}
 
 // the implicit table of the sharded path: blocks of 31744 tokens, no sync markers
 __global__ __launch_bounds__(256) void k_block_table_uniform(uint64_t T2, uint32_t nb2, BlockTab tab) {
@@ -2620,15 +2622,15 @@ static_assert(MAX_BUFFER_LENGTH % PSPLIT == 0, "parts of equal size");
 
 // (HT threads a workgroup: 256, or 1024 for a call with fewer quarter blocks than compute units -- a quarter block in one round of loads)
 template <uint32_t HT>
-__global__ __launch_bounds__(HT) void k_block_hist(const uint32_t* __restrict__ dtok, const DevScalars* sc,
-                                                    uint32_t* __restrict__ ll_freq, uint32_t* __restrict__ d_freq,
-                                                    BlockTab tab, uint32_t piece, uint32_t* __restrict__ clear, uint32_t clear_words) {
+__device__ __forceinline__ void k_block_hist_body(uint32_t bx_, uint32_t gx_, const uint32_t* dtok, const DevScalars* sc,
+                                                    uint32_t* ll_freq, uint32_t* d_freq,
+                                                    BlockTab tab, uint32_t piece, uint32_t* clear, uint32_t clear_words) {
     __shared__ uint32_t h[320];
     // (a small call's output buffer is cleared here -- k_pack ORs its bits in -- instead of by a fill of its own in front of
     // k_plan: two launches of the runtime on the way of a 0.3 ms call)
     if (clear)
-        for (uint32_t i = blockIdx.x * HT + threadIdx.x; i < clear_words; i += gridDim.x * HT) clear[i] = 0;
-    const uint32_t b = sc->nbcum[piece] + blockIdx.x / PSPLIT, q = blockIdx.x % PSPLIT;
+        for (uint32_t i = bx_ * HT + threadIdx.x; i < clear_words; i += gx_ * HT) clear[i] = 0;
+    const uint32_t b = sc->nbcum[piece] + bx_ / PSPLIT, q = bx_ % PSPLIT;
     if (b >= sc->nb || spec_failed(sc)) return;
     for (uint32_t i = threadIdx.x; i < 320; i += HT) h[i] = 0;
     __syncthreads();
@@ -2661,6 +2663,12 @@ __global__ __launch_bounds__(HT) void k_block_hist(const uint32_t* __restrict__ 
     const uint64_t slot = (uint64_t)b * PSPLIT + q;
     for (uint32_t i = threadIdx.x; i < 288; i += HT) ll_freq[slot * 288 + i] = i < NUM_LL ? h[i] : 0;
     for (uint32_t i = threadIdx.x; i < 32; i += HT) d_freq[slot * 32 + i] = i < NUM_DIST ? h[288 + i] : 0;
+}
+template <uint32_t HT>
+__global__ __launch_bounds__(HT) void k_block_hist(const uint32_t* __restrict__ dtok, const DevScalars* sc,
+                                                    uint32_t* __restrict__ ll_freq, uint32_t* __restrict__ d_freq,
+                                                    BlockTab tab, uint32_t piece, uint32_t* __restrict__ clear, uint32_t clear_words) {
+    k_block_hist_body<HT>(blockIdx.x, gridDim.x, dtok, sc, ll_freq, d_freq, tab, piece, clear, clear_words);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2915,10 +2923,10 @@ __device__ void wave_huff(HuffScratch& s, const uint32_t* freqs, uint32_t n, uin
     HT(4 + htb)
 }
 
-__global__ __launch_bounds__(128) void k_block_header(const DevScalars* sc, const uint32_t* __restrict__ ll_freq,
-                                                      const uint32_t* __restrict__ d_freq, BlockHeader* __restrict__ hdr, uint32_t piece) {
+__device__ __forceinline__ void k_block_header_body(uint32_t bx_, const DevScalars* sc, const uint32_t* ll_freq,
+                                                      const uint32_t* d_freq, BlockHeader* hdr, uint32_t piece) {
     __shared__ HdrLds s;
-    const uint32_t b = sc->nbcum[piece] + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t b = sc->nbcum[piece] + bx_, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (b >= sc->nb || spec_failed(sc)) return;
     HT_DECL
     for (uint32_t i = tid; i < 288; i += 128) {
@@ -3053,6 +3061,10 @@ __global__ __launch_bounds__(128) void k_block_header(const DevScalars* sc, cons
         for (int i = 0; i < 16; i++) ht[i] = 0;
     }
 #endif
+}
+__global__ __launch_bounds__(128) void k_block_header(const DevScalars* sc, const uint32_t* __restrict__ ll_freq,
+                                                      const uint32_t* __restrict__ d_freq, BlockHeader* __restrict__ hdr, uint32_t piece) {
+    k_block_header_body(blockIdx.x, sc, ll_freq, d_freq, hdr, piece);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3328,308 +3340,9 @@ __global__ __launch_bounds__(PKT) void k_pack(const uint8_t* __restrict__ in, ui
                                               const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ q13,
                                               uint32_t compat, uint32_t* __restrict__ out32, BlockTab tab,
                                               const uint32_t* __restrict__ ll_freq, const uint32_t* __restrict__ d_freq, uint32_t piece) {
-    constexpr uint32_t PKW = PKT / 64;
-    __shared__ PackLds<PKW> s;
-    const uint32_t b = sc->nbcum[piece] + blockIdx.x / PSPLIT, part = blockIdx.x % PSPLIT, tid = threadIdx.x;
-    if (b >= sc->nb || spec_failed(sc)) return;
-    const uint32_t gtid = part * PKT + tid;  // a stored block's bytes are spread over all parts' threads
-    constexpr uint32_t GT = PKT * PSPLIT;
-    const BlockPlan pl = plan[b];
-    const BlockHeader* h = hdr + b;
-    uint64_t bp = pl.bit_start;
-    if (pl.btype == BT_STORED) {
-        // compress.rs:59-77, stored_block.rs:13-40
-        uint64_t src = bstart[b];
-        if (q13[b] && (compat & 1)) src += WINDOW_SIZE;  // bug-for-bug (A.4 Q13)
-        uint64_t left = (uint64_t)bstart[b + 1] - bstart[b];
-        do {
-            uint64_t piece = left < (uint64_t)MAX_STORED_BLOCK_LENGTH ? left : (uint64_t)MAX_STORED_BLOCK_LENGTH;
-            bool last_piece = piece == left;
-            uint64_t hb = (bp + 3 + 7) & ~7ull;  // header bits then pad to a byte
-            if (gtid == 0) {
-                put_bits(out32, bp, (pl.bfinal && last_piece) ? 1u : 0u, 3);
-                put_bits(out32, hb, (piece & 0xffff) | (((~piece) & 0xffff) << 16), 32);
-            }
-            uint64_t ob = (hb >> 3) + 4;  // first payload byte
-            // The output words that lie wholly inside the payload belong to this piece alone: plain
-            // 4-byte stores (the source is read byte-wise, it has no alignment to speak of).  The up
-            // to three bytes before the first and after the last whole word share their words with
-            // the header or with the next block: OR.
-            const uint64_t w0 = (ob + 3) >> 2, w1 = (ob + piece) >> 2;  // whole words [w0, w1)
-            if (w1 > w0) {
-                for (uint64_t w = w0 + gtid; w < w1; w += GT) {
-                    const uint64_t i = (w << 2) - ob;  // payload offset of the word's first byte
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) v |= ((src + i + k < n) ? (uint32_t)in[src + i + k] : 0u) << (8 * k);
-                    out32[w] = v;
-                }
-                const uint64_t headn = (w0 << 2) - ob, tail0 = (w1 << 2) - ob;
-                for (uint64_t i = gtid; i < headn + (piece - tail0); i += GT) {
-                    const uint64_t j = i < headn ? i : tail0 + (i - headn);
-                    const uint64_t o = ob + j;
-                    uint32_t v = (src + j < n) ? in[src + j] : 0u;
-                    if (v) atomicOr(out32 + (o >> 2), v << (8 * (o & 3)));
-                }
-            } else {
-                for (uint64_t i = gtid; i < piece; i += GT) {
-                    uint64_t o = ob + i;
-                    uint32_t v = (src + i < n) ? in[src + i] : 0u;
-                    if (v) atomicOr(out32 + (o >> 2), v << (8 * (o & 3)));
-                }
-            }
-            bp = (ob + piece) * 8;
-            src += piece;
-            left -= piece;
-        } while (left > 0);
-        return;
-    }
-    const uint32_t nt = tab.nt[b];
-    if (part > 0 && part * PQ >= nt) return;  // (an empty block is part 0's)
-    // code tables
-    if (pl.btype == BT_FIXED) {
-        for (uint32_t i = tid; i < 288; i += PKT) s.lll[i] = (uint8_t)fixed_ll_length(i);
-        if (tid < 32) s.dl[tid] = 5;
-    } else {
-        for (uint32_t i = tid; i < 288; i += PKT) s.lll[i] = h->ll_len[i];
-        if (tid < 32) s.dl[tid] = h->d_len[tid];
-    }
-    if (tid < 20) s.cll[tid] = (pl.btype == BT_DYNAMIC && tid < 19) ? h->cl_len[tid] : 0;
-    if (tid < 48) s.cnt[tid] = 0;
-    for (uint32_t i = tid; i < PKW * PACK_WORDS; i += PKT) (&s.wbuf[0][0])[i] = 0;
-    __syncthreads();
-    // Canonical codes (huffman_table.rs:253-278; stages.h canonical_codes is the serial form) for the three
-    // tables at once: symbols per length by LDS atomics, first code of every length by one thread per table,
-    // then symbol i takes the first code of its length plus the number of symbols before it with that length.
-    for (uint32_t i = tid; i < 288; i += PKT)
-        if (s.lll[i]) atomicAdd(&s.cnt[s.lll[i]], 1u);
-    if (tid < 32 && s.dl[tid]) atomicAdd(&s.cnt[16 + s.dl[tid]], 1u);
-    if (tid < 19 && s.cll[tid]) atomicAdd(&s.cnt[32 + s.cll[tid]], 1u);
-    __syncthreads();
-    if (tid < 3) {
-        uint32_t* c = s.cnt + 16 * tid;
-        uint32_t code = 0, before = 0;  // (no symbol is counted under length 0)
-        for (uint32_t bits = 1; bits < 16; bits++) {
-            code = ((code + before) << 1) & 0xffff;
-            before = c[bits];
-            c[bits] = code;
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < 288 + 32 + 20; i += PKT) {
-        const uint8_t* len = i < 288 ? s.lll : (i < 320 ? s.dl : s.cll);
-        uint16_t* codes = i < 288 ? s.llc : (i < 320 ? s.dc : s.clc);
-        const uint32_t* first = s.cnt + (i < 288 ? 0 : (i < 320 ? 16 : 32));
-        const uint32_t k = i < 288 ? i : (i < 320 ? i - 288 : i - 320);
-        const uint32_t l = len[k];
-        uint32_t r = 0;
-        if (l) {
-            // (the symbols before k with its length, four lengths a read: byte by byte this loop was up to 287 dependent LDS
-            // reads a thread, a third of the kernel's table building; the three arrays are 4-byte aligned)
-            const uint32_t* lw = reinterpret_cast<const uint32_t*>(len);
-            const uint32_t pat = l * 0x01010101u, whole = k >> 2, rem = k & 3u;
-#pragma unroll 4
-            for (uint32_t w = 0; w < whole; w++) {
-                const uint32_t z = lw[w] ^ pat;
-                r += (uint32_t)__builtin_popcount(~(((z & 0x7f7f7f7fu) + 0x7f7f7f7fu) | z) & 0x80808080u);  // its zero bytes
-            }
-            if (rem) {
-                const uint32_t z = lw[whole] ^ pat;
-                r += (uint32_t)__builtin_popcount(~(((z & 0x7f7f7f7fu) + 0x7f7f7f7fu) | z) & 0x80808080u & ((1u << (8 * rem)) - 1u));
-            }
-        }
-        codes[k] = l ? (uint16_t)reverse_bits16((first[l] + r) & 0xffff, l) : (uint16_t)0;
-    }
-    __syncthreads();
-    // block header
-    uint32_t hdr_bits = 3;
-    if (part > 0) {
-        // Where this part's bits begin: behind the header and the tokens of the parts before it, whose sizes
-        // follow from their histograms (code length + extra bits per symbol).  A dynamic header is what is
-        // left of dyn_bits (stages.h block_costs) after all the symbols.
-        uint32_t pre = 0, all = 0;
-        for (uint32_t i = tid; i < 320; i += PKT) {
-            uint32_t len = 0;
-            if (i < NUM_LL) len = s.lll[i] + (i >= 257 ? length_extra_bits_of_code(i - 257) : 0u);
-            if (i >= 288 && i - 288 < NUM_DIST) len = s.dl[i - 288] + distance_extra_bits_of_code(i - 288);
-            for (uint32_t k = 0; k < PSPLIT; k++) {
-                const uint64_t slot = (uint64_t)b * PSPLIT + k;
-                const uint32_t f = i < 288 ? ll_freq[slot * 288 + i] : d_freq[slot * 32 + (i - 288)];
-                all += f * len;
-                if (k < part) pre += f * len;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off; off >>= 1) {
-            pre += __shfl_xor(pre, off);
-            all += __shfl_xor(all, off);
-        }
-        if ((tid & 63) == 0) {
-            s.scan[tid >> 6] = pre;
-            s.scan[PKW + (tid >> 6)] = all;
-        }
-        __syncthreads();
-        pre = 0;
-        all = 0;
-        for (uint32_t k = 0; k < PKW; k++) {
-            pre += s.scan[k];
-            all += s.scan[PKW + k];
-        }
-        __syncthreads();
-        hdr_bits = 3 + pre;
-        if (pl.btype == BT_DYNAMIC) hdr_bits += (uint32_t)(h->dyn_bits - all - s.lll[END_OF_BLOCK]);
-    } else if (pl.btype == BT_DYNAMIC) {
-        // 3 + 14 bits, the code-length code lengths (huffman_lengths.rs:329-331), then the run-length
-        // coded lengths (:338-368), one symbol per thread: bit strings, a scan of their lengths over
-        // the workgroup, OR into the output.  (One lane walking the list would wait for two dependent
-        // loads from the header in global memory per symbol.)
-        const uint32_t used = h->used_hclens, n_enc = h->n_enc;
-        if (tid == 0) {
-            uint64_t p = bp;
-            put_bits(out32, p, pl.bfinal ? 5u : 4u, 3);  // encoder_state.rs:12-13
-            p += 3;
-            put_bits(out32, p, (h->n_ll - 257) | ((h->n_d - 1) << 5) | ((used >= 4 ? used - 4 : 0) << 10), 14);
-            p += 14;
-            for (uint32_t i = 0; i < used; i++) {
-                put_bits(out32, p, s.cll[hclen_order(i)], 3);
-                p += 3;
-            }
-        }
-        uint64_t hp = bp + 17 + 3ull * used;
-        const uint32_t lane0 = tid & 63, wv0 = tid >> 6;
-        for (uint32_t i0 = 0; i0 < n_enc; i0 += PKT) {
-            const uint32_t i = i0 + tid;
-            uint64_t bits = 0;
-            uint32_t nb2 = 0;
-            if (i < n_enc) {
-                const uint32_t e = h->enc[i], kind = e >> 8, v = e & 0xff;
-                const uint32_t sym = el_symbol_index(e);
-                nb2 = s.cll[sym];
-                bits = s.clc[sym];
-                if (kind == 1) {
-                    bits |= (uint64_t)(v - 3) << nb2;
-                    nb2 += 2;
-                } else if (kind == 2) {
-                    bits |= (uint64_t)(v - 3) << nb2;
-                    nb2 += 3;
-                } else if (kind == 3) {
-                    bits |= (uint64_t)(v - 11) << nb2;
-                    nb2 += 7;
-                }
-            }
-            uint32_t incl = nb2;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                uint32_t y = __shfl_up(incl, off);
-                if (lane0 >= (uint32_t)off) incl += y;
-            }
-            if (lane0 == 63) s.scan[wv0] = incl;
-            __syncthreads();
-            uint32_t wbase = 0, total = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < PKW; k++) {
-                uint32_t y = s.scan[k];
-                if (k < wv0) wbase += y;
-                total += y;
-            }
-            put_bits(out32, hp + wbase + (incl - nb2), bits, nb2);
-            hp += total;
-            __syncthreads();
-        }
-        hdr_bits = (uint32_t)(hp - bp);
-    } else if (tid == 0) {
-        put_bits(out32, bp, pl.bfinal ? 3u : 2u, 3);  // encoder_state.rs:10-11
-    }
-    bp += hdr_bits;
-    // tokens: 4 consecutive tokens per lane and round; lengths are scanned inside the wave with
-    // shuffles and across the 4 waves through LDS (two barriers per 1024 tokens)
-    const uint64_t t0 = (uint64_t)tab.t0[b] + (uint64_t)part * PQ;
-    const uint64_t t1 = (uint64_t)tab.t0[b] + ((part + 1) * PQ < nt ? (part + 1) * PQ : nt);
-    const uint32_t lane = tid & 63, wv = tid >> 6;
-    // (a round's four tokens are fetched a round ahead, as one 16-byte load where all four exist: at the head of the round
-    // they were a memory latency per round, between two barriers)
-    auto fetch4 = [&](uint64_t tq, uint32_t* tk) {
-        if (tq + 4 <= t1) {
-            const uint4 v = *reinterpret_cast<const uint4*>(dtok + tq);  // (dword aligned is all a global load asks for)
-            tk[0] = v.x;
-            tk[1] = v.y;
-            tk[2] = v.z;
-            tk[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) tk[q] = tq + q < t1 ? dtok[tq + q] : 0u;
-        }
-    };
-    uint32_t nxt[4];
-    fetch4(t0 + 4ull * tid, nxt);
-    uint32_t* const buf = &s.wbuf[0][0];
-    bool first_shared = true;
-    for (uint64_t tb = t0; tb < t1; tb += 4 * PKT) {
-        uint64_t tq = tb + 4ull * tid;
-        uint32_t nb4[4];
-        uint64_t bits4[4];
-        uint32_t mine = 0;
-        const uint32_t cur[4] = {nxt[0], nxt[1], nxt[2], nxt[3]};
-        if (tb + 4 * PKT < t1) fetch4(tq + 4 * PKT, nxt);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            nb4[q] = 0;
-            bits4[q] = 0;
-            if (tq + q < t1) bits4[q] = token_bits(cur[q], s.llc, s.lll, s.dc, s.dl, &nb4[q]);
-            mine += nb4[q];
-        }
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            uint32_t v = __shfl_up(incl, off);
-            if (lane >= (uint32_t)off) incl += v;
-        }
-        if (lane == 63) s.scan[wv] = incl;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < PKW; k++) {
-            uint32_t v = s.scan[k];
-            if (k < wv) wbase += v;
-            total += v;
-        }
-        // The round's bits go into ONE buffer of the workgroup, word 0 = the output word the round begins in: the seams between
-        // the four waves close in LDS, the round's whole words leave by plain stores, and the word it ends in stays behind as word 0
-        // of the next round.  Only the first word of the part (shared with the header or the part before) and its last one
-        // (behind the loop) are OR-ed into the output.  (Before: a buffer per wave, its first and last word OR-ed into the output
-        // every round -- sixty-four atomics a part among the plain stores to the same lines: 101 -> 80 us without them.)
-        const uint32_t rel0 = (uint32_t)(bp & 31);
-        uint32_t rel = rel0 + wbase + (incl - mine);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            put_bits_lds(buf, rel, bits4[q], nb4[q]);
-            rel += nb4[q];
-        }
-        __syncthreads();
-        const uint64_t word0 = bp >> 5;
-        const uint32_t endbit = rel0 + total, nfull = endbit >> 5;  // whole words of the round
-        for (uint32_t w = tid; w < nfull; w += PKT) {
-            const uint32_t v = buf[w];
-            buf[w] = 0;
-            if (w == 0 && first_shared) {
-                if (v) atomicOr(out32 + word0, v);
-            } else {
-                out32[word0 + w] = v;
-            }
-        }
-        if (tid == 0 && nfull) {  // (thread 0 has done word 0 above; nobody else touches word nfull)
-            buf[0] = buf[nfull];
-            buf[nfull] = 0;
-        }
-        if (nfull) first_shared = false;
-        bp += total;
-        // (the next round writes its sums behind this round's reads of them, and into the buffer behind its own first barrier)
-    }
-    if (tid == 0 && (bp & 31)) {  // the word the part ends in: the next part's, the next block's or the end-of-block code's as well
-        const uint32_t v = buf[0];
-        if (v) atomicOr(out32 + (bp >> 5), v);
-    }
-    if (tid == 0 && (part + 1) * PQ >= nt) put_bits(out32, bp, s.llc[END_OF_BLOCK], s.lll[END_OF_BLOCK]);  // encoder_state.rs:102-105
+#define BX_ blockIdx.x
+#include "body_k_pack.inc"
+#undef BX_
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3729,65 +3442,22 @@ __global__ __launch_bounds__(256) void k_shard_costs(const BlockHeader* __restri
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t ADLER_CHUNK = 16384;
 __global__ __launch_bounds__(256) void k_adler_part(const uint8_t* __restrict__ in, uint32_t n, DevScalars* sc) {
-    __shared__ uint32_t sa[4], sb[4];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t c0 = (uint64_t)blockIdx.x * ADLER_CHUNK;
-    const uint32_t len = n - c0 < ADLER_CHUNK ? (uint32_t)(n - c0) : ADLER_CHUNK;
-    const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-    uint32_t a = 0, b = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < ADLER_CHUNK / (256 * 16); i++) {
-        const uint32_t o = (i * 256 + tid) * 16;
-        if (o >= len) break;
-        uint32_t v[4] = {0, 0, 0, 0};
-        if (o + 16 <= len && aligned) {
-            const uint4 q = *reinterpret_cast<const uint4*>(in + c0 + o);
-            v[0] = q.x;
-            v[1] = q.y;
-            v[2] = q.z;
-            v[3] = q.w;
-        } else {
-            for (uint32_t k = 0; k < 16; k++)
-                if (o + k < len) v[k >> 2] |= (uint32_t)in[c0 + o + k] << (8 * (k & 3));
-        }
-        uint32_t s = 0, w = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 16; k++) {
-            const uint32_t d = (v[k >> 2] >> (8 * (k & 3))) & 0xff;  // (bytes past the end are 0)
-            s += d;
-            w += k * d;
-        }
-        a += s;
-        b += (len - o) * s - w;  // <= 4 * 16384 * 4080 < 2^32
-    }
-    b %= 65521u;
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        b += __shfl_xor(b, off, 64);
-    }
-    if ((tid & 63) == 0) {
-        sa[tid >> 6] = a;
-        sb[tid >> 6] = b;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const uint64_t A = ((uint64_t)sa[0] + sa[1] + sa[2] + sa[3]) % 65521u;
-        const uint64_t B = ((uint64_t)sb[0] + sb[1] + sb[2] + sb[3]) % 65521u;
-        const uint64_t after = (uint64_t)n - c0 - len;
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sc->adler_a), (unsigned long long)A);
-        atomicAdd(reinterpret_cast<unsigned long long*>(&sc->adler_b), (unsigned long long)((B + (after % 65521u) * A) % 65521u));
-    }
+#define BX_ blockIdx.x
+#include "body_k_adler_part.inc"
+#undef BX_
 }
-__global__ void k_adler_fold(uint32_t n, DevScalars* sc) {
-    if (threadIdx.x || blockIdx.x) return;
+__device__ __forceinline__ void k_adler_fold_body(uint32_t bx_, uint32_t n, DevScalars* sc) {
+    if (threadIdx.x || bx_) return;
     const uint64_t a = (1 + sc->adler_a) % 65521u, b = (n + sc->adler_b) % 65521u;
     sc->adler = (uint32_t)((b << 16) | a);
 }
+__global__ void k_adler_fold(uint32_t n, DevScalars* sc) {
+    k_adler_fold_body(blockIdx.x, n, sc);
+}
 
 // zlib framing written on the device (lib.rs:182-198, zlib.rs:59-62): 78 9C, Adler-32 BE.
-__global__ void k_zlib_frame(DevScalars* sc, uint8_t* out, uint32_t trailer) {
-    if (threadIdx.x || blockIdx.x) return;
+__device__ __forceinline__ void k_zlib_frame_body(uint32_t bx_, DevScalars* sc, uint8_t* out, uint32_t trailer) {
+    if (threadIdx.x || bx_) return;
     uint64_t nbytes = (sc->total_bits + 7) / 8;
     out[0] = 0x78;
     out[1] = 0x9C;
@@ -3797,6 +3467,9 @@ __global__ void k_zlib_frame(DevScalars* sc, uint8_t* out, uint32_t trailer) {
     out[2 + nbytes + 1] = (uint8_t)(a >> 16);
     out[2 + nbytes + 2] = (uint8_t)(a >> 8);
     out[2 + nbytes + 3] = (uint8_t)a;
+}
+__global__ void k_zlib_frame(DevScalars* sc, uint8_t* out, uint32_t trailer) {
+    k_zlib_frame_body(blockIdx.x, sc, out, trailer);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3956,3 +3629,4 @@ __global__ void k_gzip_frame(DevScalars* sc, uint8_t* out, const uint8_t* hdr, u
 #include "deflate_shard.inc"
 #include "deflate_long.inc"
 #include "deflate_multi.inc"
+#include "deflate_batch.inc"

@@ -625,6 +625,10 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
         if (value > 2) return MI355_E_ARG;
         c->stage_clocks = (int)value;
         return MI355_OK;
+    case MI355_CFG_BATCH_BYTES:
+        if (value < (1ull << 20) || value > (1ull << 30)) return MI355_E_ARG;
+        c->batch_bytes = value;
+        return MI355_OK;
     case MI355_CFG_SORT_RANKS:
         if (value > 1) return MI355_E_ARG;
         if (value == 1 && !c->lds_order_ok) return MI355_E_UNSUPPORTED;  // the device failed the self-test

@@ -1462,5 +1462,31 @@ MI355_HD uint64_t token_bits(uint32_t tok, const LLCodes& llc, const LLLens& lll
     return bits;
 }
 
+// The flat grids of the batched kernels (deflate_batch.inc): a launch runs the workgroups of every item of a batch back to back,
+// and workgroup `bx` belongs to the last item i with pre[i] <= bx.  pre: the stage's running sum of workgroups per item,
+// n_items + 1 entries, pre[0] = 0, bx < pre[n_items]; an item without workgroups shares its entry with the item behind it.
+// 64 places per round, one per lane of a wave (the ballot of "at or below bx" is a run of lanes from lane 0): two rounds find
+// the item among 4096.  Every lane of the wave calls it and gets the same answer.
+MI355_HD uint32_t batch_item_of(const uint32_t* pre, uint32_t n_items, uint32_t bx) {
+    uint32_t lo = 0, hi = n_items;  // the item is in [lo, hi); pre[lo] <= bx
+    while (hi - lo > 1) {
+        const uint32_t step = (hi - lo + 63) / 64;
+        uint32_t last = 0;  // the last place at or below bx (place 0, lo itself, always is)
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t at = lo + (threadIdx.x & 63) * step;
+        const uint64_t m = __ballot(at < hi && pre[at] <= bx);
+        last = 63u - (uint32_t)__clzll((long long)m);
+#else
+        for (uint32_t l = 0; l < 64; l++) {
+            const uint32_t at = lo + l * step;
+            if (at < hi && pre[at] <= bx) last = l;
+        }
+#endif
+        lo += last * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    return lo;
+}
+
 }  // namespace mi355
 #endif

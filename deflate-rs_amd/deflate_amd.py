@@ -99,6 +99,19 @@ class CompressionOptions:
         return Opts(self.max_hash_checks, self.lazy_if_less_than, int(self.matching_type), wrapper, compat, flush)
 
 
+class BatchItem(C.Structure):
+    """mi355_batch_item"""
+    _fields_ = [("in_", C.c_void_p), ("in_len", C.c_size_t), ("out", C.c_void_p), ("out_cap", C.c_size_t),
+                ("out_len", C.c_size_t), ("status", C.c_int)]
+
+
+class BatchInfo(C.Structure):
+    """mi355_batch_info"""
+    _fields_ = [("n_items", C.c_uint64), ("in_len", C.c_uint64), ("out_len", C.c_uint64), ("n_batched", C.c_uint32),
+                ("n_single", C.c_uint32), ("n_q1_single", C.c_uint32), ("n_spec_single", C.c_uint32),
+                ("sub_batches", C.c_uint32), ("total_ms", C.c_float)]
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -190,6 +203,9 @@ def load():
     L.mi355_deflate_stream_held_bytes.argtypes = [C.c_void_p]
     L.mi355_deflate_stream_held_bytes.restype = C.c_uint64
     L.mi355_deflate_stream_free.restype = None
+    L.mi355_deflate_encode_batch.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts)]
+    L.mi355_deflate_encode_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts), C.c_void_p]
+    L.mi355_deflate_last_batch_info.argtypes = [C.c_void_p, C.POINTER(BatchInfo)]
     _lib = L
     return L
 
@@ -212,6 +228,7 @@ EXPORTED = [
     "mi355_device_count", "mi355_multi_create", "mi355_multi_destroy", "mi355_multi_devices", "mi355_multi_ctx", "mi355_multi_last_error",
     "mi355_multi_layout", "mi355_deflate_encode_multi", "mi355_deflate_encode_multi_device", "mi355_multi_last_trace",
     "mi355_multi_stitch_info",
+    "mi355_deflate_encode_batch", "mi355_deflate_encode_batch_device", "mi355_deflate_last_batch_info",
 ]
 
 
@@ -243,7 +260,7 @@ class Context:
         raise DeflateError(rc, load().mi355_deflate_last_error(self._h).decode())
 
     CFG_RANGE_BYTES, CFG_LONG_FROM, CFG_SORT_RANKS, CFG_HOST_STREAMING, CFG_MULTI_STITCH, CFG_STEPS_IN_EMIT = 1, 2, 3, 4, 5, 6
-    CFG_HOST_BOUNCE, CFG_HOST_THREADS, CFG_STAGE_CLOCKS = 7, 8, 9
+    CFG_HOST_BOUNCE, CFG_HOST_THREADS, CFG_STAGE_CLOCKS, CFG_BATCH_BYTES = 7, 8, 9, 10
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -316,6 +333,68 @@ class Context:
             self._err(rc)
         return n.value
 
+    def _batch_error(self, rc, items):
+        bad = [k for k in range(len(items)) if items[k].status != OK]
+        if not bad:
+            self._err(rc)
+        raise DeflateError(rc, "batch item %d failed (status %d): %s" % (bad[0], items[bad[0]].status,
+                                                                        load().mi355_deflate_last_error(self._h).decode()))
+
+    def encode_batch(self, datas, options=Compression.Default, wrapper=0, compat=0):
+        """Many host inputs in one batched call (mi355_deflate_encode_batch); a list of bytes, item i's exactly what
+        encode(datas[i]) gives.  Raises DeflateError naming the first failing index."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(wrapper, compat, 0)
+        datas = [bytes(d) for d in datas]
+        items = (BatchItem * max(len(datas), 1))()
+        outs = []
+        for k, d in enumerate(datas):
+            cap = L.mi355_deflate_bound_ex(len(d), wrapper, 0, 0)
+            out = (C.c_uint8 * max(cap, 1))()
+            outs.append(out)
+            items[k].in_ = C.cast(C.c_char_p(d), C.c_void_p) if d else C.c_void_p(0)
+            items[k].in_len = len(d)
+            items[k].out = C.cast(out, C.c_void_p)
+            items[k].out_cap = cap
+        rc = L.mi355_deflate_encode_batch(self._h, items, len(datas), C.byref(o))
+        if rc != OK:
+            self._batch_error(rc, items[: len(datas)])
+        return [bytes(memoryview(outs[k])[: items[k].out_len]) for k in range(len(datas))]
+
+    def encode_batch_device(self, ins, outs=None, options=Compression.Default, wrapper=0, compat=0, stream=0, check=True):
+        """Device inputs in one batched call (mi355_deflate_encode_batch_device).  ins: torch tensors on this context's device
+        or (pointer, length) pairs; outs: the same for the outputs (None: uint8 tensors of mi355_deflate_bound_ex bytes, made
+        here).  Returns (outs, lengths, statuses).  check: raise DeflateError naming the first failing index."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(wrapper, compat, 0)
+
+        def ptr_len(x):
+            if isinstance(x, tuple):
+                return int(x[0]), int(x[1])
+            return int(x.data_ptr()), int(x.numel() * x.element_size())
+        ins_pl = [ptr_len(x) for x in ins]
+        if outs is None:
+            import torch
+            dev = ins[0].device if ins and not isinstance(ins[0], tuple) else torch.device("cuda", 0)
+            outs = [torch.empty(L.mi355_deflate_bound_ex(n, wrapper, 0, 0), dtype=torch.uint8, device=dev) for _, n in ins_pl]
+        outs_pl = [ptr_len(x) for x in outs]
+        items = (BatchItem * max(len(ins_pl), 1))()
+        for k, ((ip, n), (op, cap)) in enumerate(zip(ins_pl, outs_pl)):
+            items[k].in_ = C.c_void_p(ip if n else 0)
+            items[k].in_len = n
+            items[k].out = C.c_void_p(op)
+            items[k].out_cap = cap
+        rc = L.mi355_deflate_encode_batch_device(self._h, items, len(ins_pl), C.byref(o), C.c_void_p(stream))
+        if rc != OK and check:
+            self._batch_error(rc, items[: len(ins_pl)])
+        return outs, [items[k].out_len for k in range(len(ins_pl))], [items[k].status for k in range(len(ins_pl))]
+
+    def batch_info(self):
+        """mi355_deflate_last_batch_info as a dict"""
+        i = BatchInfo()
+        load().mi355_deflate_last_batch_info(self._h, C.byref(i))
+        return {k: getattr(i, k) for k, _ in BatchInfo._fields_}
+
     def info(self):
         i = Info()
         load().mi355_deflate_last_info(self._h, C.byref(i))
@@ -376,6 +455,25 @@ def deflate_bytes_zlib_conf(data, options, ctx=None):
 def deflate_bytes_zlib(data, ctx=None):
     """src/lib.rs:216-218"""
     return deflate_bytes_zlib_conf(data, Compression.Default, ctx)
+
+
+# ---- the same, many inputs in one batched call (mi355_deflate_encode_batch) --------------------
+def deflate_bytes_batch_conf(datas, options, ctx=None):
+    """deflate_bytes_conf of every input, in one batch"""
+    return (ctx or default_context()).encode_batch(datas, options, wrapper=0)
+
+
+def deflate_bytes_batch(datas, ctx=None):
+    return deflate_bytes_batch_conf(datas, Compression.Default, ctx)
+
+
+def deflate_bytes_zlib_batch_conf(datas, options, ctx=None):
+    """deflate_bytes_zlib_conf of every input, in one batch"""
+    return (ctx or default_context()).encode_batch(datas, options, wrapper=1)
+
+
+def deflate_bytes_zlib_batch(datas, ctx=None):
+    return deflate_bytes_zlib_batch_conf(datas, Compression.Default, ctx)
 
 
 # GzBuilder::new().into_header() of crate gzip-header 1.0 (the crate is not in the reference tree)

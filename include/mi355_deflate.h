@@ -152,7 +152,9 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *                          call, 2 = for calls of 32 MiB or more.  They are events between the kernels of a call, each 5.7 us of
  *                          idle queue -- a tenth of a 167 KB call, 0.7 % of a 100 MB one; without them stage_ms and match_ms read 0
  *                          and total_ms is the host's clock from the call's first launch to the return of its last wait.
- *                          (The environment variable MI355_STAGE_CLOCKS sets the default: a measuring aid.) */
+ *                          (The environment variable MI355_STAGE_CLOCKS sets the default: a measuring aid.)
+ *   MI355_CFG_BATCH_BYTES  input bytes of one launch set of mi355_deflate_encode_batch[_device] (default 256 MiB; 1 MiB .. 1 GiB):
+ *                          a batch with more is cut into consecutive sub-batches.  Same bytes either way. */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -162,6 +164,7 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_HOST_BOUNCE 7
 #define MI355_CFG_HOST_THREADS 8
 #define MI355_CFG_STAGE_CLOCKS 9
+#define MI355_CFG_BATCH_BYTES 10
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
@@ -237,6 +240,44 @@ typedef struct {
     uint64_t bit_start;
 } mi355_block_info;
 int mi355_deflate_last_blocks(mi355_deflate_ctx* ctx, mi355_block_info* out, size_t cap, size_t* n_blocks);
+
+/* ---- batched encode: many independent inputs, one set of launches -----------------------------
+ * Item i's output is byte for byte what mi355_deflate_encode gives for that item alone with the same opts (whatever the
+ * other items, their order or their number).  One opts for the whole batch: every level, wrapper 0 (raw) or 1 (zlib),
+ * MI355_FLUSH_FINISH; wrapper 2 or a sync flush is MI355_E_ARG, lazy_if_less_than < 3 with Lazy MI355_E_UNSUPPORTED.
+ * Items of up to 2 MiB at the levels with a hash table are encoded together by the batched kernels; longer items, the
+ * levels without a hash (RLE, Huffman-only), empty items and the items whose first block fires the hash re-warm (A.4 Q1)
+ * or whose speculative parse fails go through the one-input path after them.
+ * An item with out_cap < mi355_deflate_bound_ex(in_len, opts->wrapper, 0, 0) gets MI355_E_OUT_TOO_SMALL and the size needed in
+ * out_len; an item may get MI355_E_REF_PANIC under MI355_COMPAT_Q13.  Neither disturbs the other items.  The call returns
+ * MI355_OK when every item is OK, else the status of the first failing item; errors of the call itself (NULL items with
+ * n_items > 0, NULL opts, an item without buffers, bad options) are MI355_E_ARG and write no item.
+ * _device: in / out are device pointers (out 4-byte aligned); hip_stream NULL = the context's stream; the call returns
+ * after the stream has drained.  Without _device they are host pointers.
+ * After a batch, mi355_deflate_last_info describes the batch as a whole (sums) and mi355_deflate_last_blocks reports 0 blocks. */
+typedef struct {
+    const void* in;    /* host pointer (mi355_deflate_encode_batch) or device pointer (_device) */
+    size_t in_len;
+    void* out;         /* host / device; on the device entry 4-byte aligned */
+    size_t out_cap;    /* >= mi355_deflate_bound_ex(in_len, opts->wrapper, 0, 0) */
+    size_t out_len;    /* written: bytes produced, or the size needed after MI355_E_OUT_TOO_SMALL */
+    int status;        /* written: MI355_OK or this item's MI355_E_* */
+} mi355_batch_item;
+
+typedef struct {
+    uint64_t n_items, in_len, out_len;   /* sums over the items */
+    uint32_t n_batched;                  /* items encoded by the batched kernels */
+    uint32_t n_single;                   /* items sent through the one-input path */
+    uint32_t n_q1_single, n_spec_single; /* of n_single: Q1 re-warm fired / speculative entries failed */
+    uint32_t sub_batches;                /* launch sets the batch was cut into */
+    float total_ms;                      /* host clock over the call */
+} mi355_batch_info;
+
+int mi355_deflate_encode_batch(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                               const mi355_deflate_opts* opts);
+int mi355_deflate_encode_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                                      const mi355_deflate_opts* opts, void* hip_stream);
+int mi355_deflate_last_batch_info(mi355_deflate_ctx* ctx, mi355_batch_info* info);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range

@@ -17,6 +17,16 @@ pub struct Mi355Opts {
     compat: u8,
     flush: u8, // 0 Finish, 1 Sync
 }
+/// include/mi355_deflate.h: mi355_batch_item
+#[repr(C)]
+struct Mi355BatchItem {
+    input: *const u8,
+    in_len: usize,
+    out: *mut u8,
+    out_cap: usize,
+    out_len: usize,
+    status: c_int,
+}
 #[repr(C)]
 pub struct Ctx {
     _p: [u8; 0],
@@ -51,6 +61,11 @@ extern "C" {
     fn mi355_multi_create(devices: *const c_int, n_devices: c_int, out: *mut *mut Multi) -> c_int;
     fn mi355_deflate_encode_multi(m: *mut Multi, input: *const u8, in_len: usize, opts: *const Mi355Opts, gz_hdr: *const u8,
                                   gz_len: usize, out: *mut u8, out_cap: usize, out_len: *mut usize) -> c_int;
+    // many independent inputs in one set of launches (include/mi355_deflate.h, "batched encode")
+    fn mi355_deflate_encode_batch(ctx: *mut Ctx, items: *mut Mi355BatchItem, n_items: usize, opts: *const Mi355Opts) -> c_int;
+    fn mi355_deflate_encode_batch_device(ctx: *mut Ctx, items: *mut Mi355BatchItem, n_items: usize, opts: *const Mi355Opts,
+                                         hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn mi355_deflate_last_batch_info(ctx: *mut Ctx, info: *mut std::ffi::c_void) -> c_int;
     fn mi355_device_count() -> c_int; // (the shim links libmi355deflate.so only: no HIP symbol is named from Rust)
 }
 
@@ -185,6 +200,30 @@ pub fn deflate_bytes_zlib_conf<O: Into<CompressionOptions>>(input: &[u8], option
 /// src/lib.rs:216-218
 pub fn deflate_bytes_zlib(input: &[u8]) -> Vec<u8> {
     deflate_bytes_zlib_conf(input, Compression::Default)
+}
+fn batch(inputs: &[&[u8]], o: Mi355Opts) -> Vec<Vec<u8>> {
+    unsafe {
+        let mut outs: Vec<Vec<u8>> = inputs.iter().map(|i| Vec::with_capacity(mi355_deflate_bound_ex(i.len(), o.wrapper as c_int, 0, 0))).collect();
+        let mut items: Vec<Mi355BatchItem> = inputs
+            .iter()
+            .zip(outs.iter_mut())
+            .map(|(i, v)| Mi355BatchItem { input: i.as_ptr(), in_len: i.len(), out: v.as_mut_ptr(), out_cap: v.capacity(), out_len: 0, status: 0 })
+            .collect();
+        let rc = mi355_deflate_encode_batch(std::ptr::null_mut(), items.as_mut_ptr(), items.len(), &o);
+        assert!(rc == 0, "mi355_deflate_encode_batch failed: {}", rc);
+        for (v, it) in outs.iter_mut().zip(items.iter()) {
+            v.set_len(it.out_len);
+        }
+        outs
+    }
+}
+/// deflate_bytes_conf (src/lib.rs:137-147) of every input, in one batched call: item i is deflate_bytes_conf(inputs[i], options)
+pub fn deflate_bytes_batch_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O) -> Vec<Vec<u8>> {
+    batch(inputs, c_opts(options.into(), 0))
+}
+/// deflate_bytes_zlib_conf (src/lib.rs:182-198) of every input, in one batched call
+pub fn deflate_bytes_zlib_batch_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O) -> Vec<Vec<u8>> {
+    batch(inputs, c_opts(options.into(), 1))
 }
 /// src/lib.rs:242-267
 #[cfg(feature = "gzip")]
