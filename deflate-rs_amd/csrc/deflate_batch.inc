@@ -184,9 +184,7 @@ struct BatchView {
 
 // Can the batched kernels take this item?  (Else: the one-input path, after the launch sets.)
 bool batch_takes(const ParseCfg& cfg, uint64_t n) {
-    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
-    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
-    return MI355_SMALL_TAIL && hashing && !(cfg.use_quarter && cq == 0) && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
+    return MI355_SMALL_TAIL && cfg_hashing(cfg) && !(cfg.use_quarter && cfg_cq(cfg) == 0) && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
 }
 
 enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
@@ -195,8 +193,8 @@ enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
 int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const mi355_deflate_opts* o, const ParseCfg& cfg,
                      hipStream_t st, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
     const bool zlib = o->wrapper == 1;
-    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
-    const bool has_q = cfg.use_quarter && cq;
+    const uint32_t cq = cfg_cq(cfg);
+    const bool has_q = cfg_has_q(cfg);
     // the items' workspaces, one behind the other in the context's one workspace
     std::vector<uint64_t> ws_off(k + 1, 0);
     for (uint32_t i = 0; i < k; i++) ws_off[i + 1] = ws_off[i] + carve(nullptr, v[i].n, cfg.use_quarter).bytes;
@@ -222,9 +220,9 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     uint64_t epochs = 0;
     for (uint32_t i = 0; i < k; i++) epochs += (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
     const uint32_t cus = c->n_cu ? c->n_cu : 256u;
-    uint32_t split = match3_split(epochs, c->n_cu);
-    const bool single = split >= MI355_M3_SPLIT_MAX && epochs * split * 2 <= cus;
-    if (single) split *= 2;
+    const WalkPlan plan = walk_plan(epochs, c->n_cu);
+    const bool single = plan.single;
+    const uint32_t split = single ? plan.split * 2 : plan.split;
     for (uint32_t s = 0; s < BS_N; s++) hpre[(size_t)s * (k + 1)] = 0;
     for (uint32_t i = 0; i < k; i++) {
         const Workspace w = carve(c->ws + ws_off[i], v[i].n, cfg.use_quarter);
@@ -325,9 +323,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             c->err = "batched walk: a bucket out of order with ballot ranks";
             return MI355_E_HIP;
         }
-        c->sort_mode = 0;
-        c->lds_order_ok = false;
-        c->sort_break = 0;
+        sort_fell_back(c);
         return batch_launch_set(c, v, k, o, cfg, st, out_len, outcome, sums);
     }
     for (uint32_t i = 0; i < k; i++) {
@@ -342,7 +338,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             outcome[i] = BO_PANIC;
         else {
             outcome[i] = BO_OK;
-            out_len[i] = (size_t)((s.total_bits + 7) / 8) + (zlib ? 6 : 0);
+            out_len[i] = stream_bytes(s.total_bits, o->wrapper, 0, false);
             sums->T += s.T;
             sums->nb += s.nb;
             sums->n_stored += s.n_stored;
@@ -364,14 +360,7 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
         return MI355_E_STATE;
     }
     ParseCfg cfg;
-    cfg.checks = o->max_hash_checks;
-    cfg.lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;
-    cfg.mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);
-    cfg.use_quarter = (cfg.mode == MODE_LAZY && cfg.lazy_lt > 32) ? 1 : 0;
-    if (cfg.mode == MODE_LAZY && cfg.lazy_lt < 3) {
-        c->err = "lazy_if_less_than < 3 with Lazy matching is not supported (SURVEY A.4 Q3)";
-        return MI355_E_UNSUPPORTED;
-    }
+    if (const int rc = parse_cfg(c, o, &cfg)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     c->last_plan = nullptr;  // (the workspace is carved again below)
     c->last_nb = 0;
@@ -498,12 +487,7 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
     memset(&info, 0, sizeof info);
     info.in_len = bi.in_len;
     info.out_len = bi.out_len;
-    info.n_tokens = sums.T;
-    info.n_blocks = sums.nb;
-    info.n_stored = sums.n_stored;
-    info.n_fixed = sums.n_fixed;
-    info.n_dynamic = sums.n_dynamic;
-    info.q13_hits = sums.q13_hits;
+    info_from_scalars(&info, sums);
     info.q1_rewarm = q1_any ? 1u : 0u;
     info.spec_fallback = spec_any;
     info.passes = 1;

@@ -487,11 +487,15 @@ bool spec_entries_failed(mi355_deflate_ctx* c) {
     return true;
 }
 
-bool sort_order_failed(mi355_deflate_ctx* c) {
-    if (!reinterpret_cast<const DevState*>(c->h_sc)->sort_bad) return false;
+// (the state change alone: the batched call keeps the flag per item and finds it cleared with the items' states)
+void sort_fell_back(mi355_deflate_ctx* c) {
     c->sort_mode = 0;
     c->lds_order_ok = false;
     c->sort_break = 0;
+}
+bool sort_order_failed(mi355_deflate_ctx* c) {
+    if (!reinterpret_cast<const DevState*>(c->h_sc)->sort_bad) return false;
+    sort_fell_back(c);
     (void)hipMemsetAsync(sort_bad_flag(c), 0, sizeof(uint32_t), c->own_stream);
     (void)hipStreamSynchronize(c->own_stream);
     reinterpret_cast<DevState*>(c->h_sc)->sort_bad = 0;
@@ -506,6 +510,48 @@ constexpr uint64_t STAGE_CLOCKS_FROM = 32ull << 20;
 #endif
 bool stage_clocks_on(const mi355_deflate_ctx* c, uint64_t n) { return c->stage_clocks == 1 || (c->stage_clocks == 2 && n >= STAGE_CLOCKS_FROM); }
 
+// ---- what the drivers share: the single pass, the streamed host call, the shard phases, the batched call -----------------------
+// Each of the launch_* functions queues launches on the stream it is given and decides nothing about the call.
+
+// The parse settings of a call's options.  Quirk Q3 (lazy_if_less_than < 3 with Lazy matching) is refused.
+int parse_cfg(mi355_deflate_ctx* c, const mi355_deflate_opts* o, ParseCfg* cfg) {
+    cfg->checks = o->max_hash_checks;
+    cfg->lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;  // deflate_state.rs:105
+    cfg->mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);  // lz77.rs:211-231
+    cfg->use_quarter = (cfg->mode == MODE_LAZY && cfg->lazy_lt > 32) ? 1 : 0;
+    if (cfg->mode == MODE_LAZY && cfg->lazy_lt < 3) {
+        c->err = "lazy_if_less_than < 3 with Lazy matching is not supported (SURVEY A.4 Q3)";
+        return MI355_E_UNSUPPORTED;
+    }
+    return MI355_OK;
+}
+// (the level builds chains and walks them; the budget of the quarter table; whether that table is walked at all)
+inline bool cfg_hashing(const ParseCfg& cfg) { return cfg.mode != MODE_RLE && cfg.checks > 0; }
+inline uint32_t cfg_cq(const ParseCfg& cfg) { return cfg.use_quarter ? (cfg.checks >> 2) : 0; }
+inline bool cfg_has_q(const ParseCfg& cfg) { return cfg.use_quarter && cfg_cq(cfg); }
+
+// no re-warm, no flush points, no write-pattern quirks: every call but a stream's and a second pass
+constexpr HashOverride NO_HASH_OVERRIDE = {0, 0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+
+// ---- after the wait ----
+void info_from_scalars(mi355_deflate_info* info, const DevScalars& s) {
+    info->n_tokens = s.T;
+    info->n_blocks = s.nb;
+    info->n_stored = s.n_stored;
+    info->n_fixed = s.n_fixed;
+    info->n_dynamic = s.n_dynamic;
+    info->q13_hits = s.q13_hits;
+    info->spec_repaired = 0;
+    for (uint32_t k = 0; k < PIECES_MAX; k++) info->spec_repaired += s.n_fix[k];
+}
+// bytes of the stream with its frame (sync_tail: the call ends in a sync flush, the trailer is not written yet)
+size_t stream_bytes(uint64_t total_bits, uint32_t wrapper, size_t gz_len, bool sync_tail) {
+    const size_t body = (size_t)((total_bits + 7) / 8);
+    if (wrapper == 1) return body + (sync_tail ? 2 : 6);
+    if (wrapper == 2) return body + gz_len + (sync_tail ? 0 : 8);
+    return body;
+}
+
 void launch_sort(mi355_deflate_ctx* c, hipStream_t st, uint32_t epochs, const uint8_t* d_in, uint32_t n32, const HashOverride& ov,
                  uint16_t* S, uint16_t* B, uint32_t e0, const SortInit* init = nullptr) {
     if (epochs == 0) return;
@@ -516,20 +562,34 @@ void launch_sort(mi355_deflate_ctx* c, hipStream_t st, uint32_t epochs, const ui
         hipLaunchKernelGGL(k_sort<0>, dim3(epochs), dim3(1024), 0, st, d_in, n32, ov, S, B, e0, 1u, in0);
 }
 
+// The walk's plan for `n_ep` epochs: `split` workgroups per epoch (match3_split), and `single` for the launch that walks both
+// tables at once (a small call, the batched call): twice the parts and ONE batch a wave instead of a pair where that still is one
+// round of workgroups.  A small call's walk
+// is the latency of its slowest lane's chain of step blocks, and a wave with one fibre steps through it at twice the
+// rate (pg11.txt 0.213 -> 0.202 ms; MI355_M3_SINGLE=0: the pair, a measuring aid)
+struct WalkPlan {
+    uint32_t split;
+    bool single;
+};
+WalkPlan walk_plan(uint64_t n_ep, uint32_t n_cu) {
+    static const bool single_env = !(getenv("MI355_M3_SINGLE") && getenv("MI355_M3_SINGLE")[0] == '0');
+    const uint32_t cus = n_cu ? n_cu : 256u;
+    const uint32_t split = match3_split(n_ep, n_cu);
+    return WalkPlan{split, single_env && split >= MI355_M3_SPLIT_MAX && n_ep * split * 2 <= cus};
+}
+
 // the walk over `ne` sorted epochs from e_first on (split: workgroups per epoch; the results go out in the order of the sorted
 // arrays and are turned round at the end of an epoch when an epoch is one workgroup's)
-void launch_walk(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint32_t n32, const uint16_t* S, Workspace& w, const ParseCfg& cfg, bool has_q,
-                 uint32_t cq, int aligned16, SegEnds sg, const HashOverride& ov, uint32_t e_first, uint32_t ne, uint32_t split) {
+void launch_walk(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint32_t n32, const uint16_t* S, Workspace& w, const ParseCfg& cfg,
+                 int aligned16, SegEnds sg, const HashOverride& ov, uint32_t e_first, uint32_t ne) {
+    const WalkPlan plan = walk_plan(ne, c->n_cu);
+    const uint32_t split = plan.split, cq = cfg_cq(cfg);
+    const bool has_q = cfg_has_q(cfg);
     // (k_match3 borrows the token arrays, which nothing has written yet, for the results in sorted order: 4 B per position each)
     uint32_t* const ms = split == 1 ? w.tokbuf : nullptr;
     uint32_t* const mqs = split == 1 ? w.dtok : nullptr;
     if (MI355_SWZ_BANKS && ne * split <= M3_BOTH_UNITS) {  // small: both tables in one launch
-        // Twice the parts and ONE batch a wave instead of a pair where that still is one round of workgroups: a small call's walk
-        // is the latency of its slowest lane's chain of step blocks, and a wave with one fibre steps through it at twice the
-        // rate (pg11.txt 0.213 -> 0.202 ms; MI355_M3_SINGLE=0: the pair, a measuring aid)
-        static const bool single_env = !(getenv("MI355_M3_SINGLE") && getenv("MI355_M3_SINGLE")[0] == '0');
-        const uint32_t cus = c->n_cu ? c->n_cu : 256u;
-        const bool single = single_env && split >= MI355_M3_SPLIT_MAX && ne * split * 2 <= cus;
+        const bool single = plan.single;
         const uint32_t sp = single ? split * 2 : split;
         uint32_t* const ms1 = sp == 1 ? w.tokbuf : nullptr;
         uint32_t* const mqs1 = sp == 1 ? w.dtok : nullptr;
@@ -567,6 +627,83 @@ void launch_walk(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint
     }
 }
 
+// A range of segments to parse, as plain data: all segments of a single pass, a piece of the streamed call, a shard's range.
+struct SegRange {
+    uint32_t seg_hi;        // the segments [piece.seg_lo, seg_hi)
+    Piece piece;
+    const uint8_t* d_in;    // the buffer, and the parse range in it: n positions from pos0 on, of n_total
+    uint32_t n, pos0, n_total;
+    uint32_t runup0;        // 1: the range's first segment has history in front of it to run up through
+    SegEnds sg;
+    const uint16_t* steps;  // the restart steps (k_adv, k_rle), or nullptr: k_emit works them out itself
+    uint32_t* E0;           // where the segments are entered ...
+    uint32_t* xs;           // ... and where they were left
+    uint32_t* fixlist;      // the entries to repair, and how many
+    uint32_t* n_fix;
+    uint32_t* scan_part;
+    uint32_t* tend;         // (k_scan_b: the totals of a call with one segment end, or nullptr)
+    uint32_t* pb;
+};
+
+// Every segment of the range finds its entry itself (a run-up of SPEC_W positions in front of it) and says where it was left.
+void launch_spec_emit(hipStream_t st, const Workspace& w, const ParseCfg& cfg, const SegRange& r) {
+    const SpecFix fx{r.fixlist, w.badmap, r.n_fix};
+    MI355_LAUNCH_EMIT(1, r.steps, dim3(cdiv(r.seg_hi - r.piece.seg_lo, 4)), st, r.d_in, r.n, r.seg_hi, w.M, cfg.use_quarter ? w.Mq : nullptr, cfg,
+                       r.steps, r.E0, w.tokbuf, w.cnt, r.pos0, r.n_total, r.sg, r.xs, fx, r.runup0, r.piece.seg_lo);
+}
+// The speculative entries of the range: k_emit<1>; then a handful of entries that did not check out (seams of pieces of different
+// kinds, a short periodic stretch) are parsed again from where the segment before them was left; what is still wrong then
+// fails k_scan_a's check of the chain of entries and exits (DevState::spec_bad).
+void launch_spec_entries(mi355_deflate_ctx* c, hipStream_t st, const Workspace& w, const ParseCfg& cfg, const SegRange& r) {
+    const uint32_t lo = r.piece.seg_lo, ns = r.seg_hi - lo;
+    const SpecFix fx{r.fixlist, w.badmap, r.n_fix};
+    launch_spec_emit(st, w, cfg, r);
+    hipLaunchKernelGGL(k_spec_check, dim3(cdiv(ns, 256)), dim3(256), 0, st, r.seg_hi, (const uint32_t*)r.E0, (const uint32_t*)r.xs, w.badmap,
+                       r.fixlist, r.n_fix, lo);
+    MI355_LAUNCH_EMIT(2, r.steps, dim3(FIX_MAX / 4), st, r.d_in, r.n, r.seg_hi, w.M, cfg.use_quarter ? w.Mq : nullptr, cfg, r.steps, r.E0,
+                       w.tokbuf, w.cnt, r.pos0, r.n_total, r.sg, r.xs, fx, 0u, 0u);
+    hipLaunchKernelGGL(k_scan_a, dim3(cdiv(ns, 1024)), dim3(1024), 0, st, r.seg_hi, w.cnt, r.scan_part, (const uint32_t*)r.E0,
+                       (const uint32_t*)r.xs, &reinterpret_cast<DevState*>(c->d_sc)->spec_bad, lo);
+}
+// The token scan of the range: where every segment's tokens go in the stream, and the tokens there.  `exact`: the entries came from
+// the exit tables, there is no chain to check and k_scan_a has not run yet.
+void launch_token_scan(mi355_deflate_ctx* c, hipStream_t st, const Workspace& w, const SegRange& r, bool exact) {
+    const uint32_t lo = r.piece.seg_lo, ns = r.seg_hi - lo;
+    if (exact)
+        hipLaunchKernelGGL(k_scan_a, dim3(cdiv(ns, 1024)), dim3(1024), 0, st, r.seg_hi, w.cnt, r.scan_part, (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr, (uint32_t*)nullptr, lo);
+    hipLaunchKernelGGL(k_scan_b, dim3(cdiv(ns, 1024)), dim3(1024), 0, st, r.seg_hi, w.cnt, r.scan_part, w.base, c->d_sc, r.tend, r.pb, r.piece);
+    hipLaunchKernelGGL(k_compact, dim3(cdiv(ns, 4)), dim3(256), 0, st, r.seg_hi, w.tokbuf, w.cnt, w.base, w.dtok, c->d_sc, lo);
+}
+
+// Adler-32 / CRC-32 of d_in[0..n) into the scalars (`part`: a word per CRC_CHUNK bytes)
+void launch_adler(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint64_t n) {
+    const uint32_t nch = cdiv(n, ADLER_CHUNK);
+    if (nch) hipLaunchKernelGGL(k_adler_part, dim3(nch), dim3(256), 0, st, d_in, (uint32_t)n, c->d_sc);
+    hipLaunchKernelGGL(k_adler_fold, dim3(1), dim3(64), 0, st, (uint32_t)n, c->d_sc);
+}
+void launch_crc(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint64_t n, uint32_t* part) {
+    const uint32_t nch = cdiv(n, CRC_CHUNK);
+    if (nch) {
+        hipLaunchKernelGGL(k_crc_part, dim3(cdiv(nch, 256)), dim3(256), 0, st, d_in, (uint32_t)n, part);
+        hipLaunchKernelGGL(k_crc_fold, dim3(cdiv(nch, 256)), dim3(256), 0, st, (uint32_t)n, nch, part, c->d_sc);
+    }
+}
+// The checksum of the input and the frame around the stream (wrapper 1: zlib, 2: gzip with the caller's header; `final`: with the trailer).
+int launch_frame_tail(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint64_t n, uint32_t wrapper, const Workspace& w,
+                      const uint8_t* gz_hdr, size_t gz_len, uint8_t* d_out, bool final) {
+    if (wrapper == 1) {
+        launch_adler(c, st, d_in, n);
+        hipLaunchKernelGGL(k_zlib_frame, dim3(1), dim3(64), 0, st, c->d_sc, d_out, final ? 1u : 0u);
+    }
+    if (wrapper == 2) {
+        HIPCHK(c, hipMemcpyAsync(w.gz_hdr, gz_hdr, gz_len, hipMemcpyHostToDevice, st));
+        launch_crc(c, st, d_in, n, w.crc_part);
+        hipLaunchKernelGGL(k_gzip_frame, dim3(1), dim3(64), 0, st, c->d_sc, d_out, w.gz_hdr, (uint32_t)gz_len, (uint32_t)n, final ? 1u : 0u);
+    }
+    return MI355_OK;
+}
+
 // links + match table (chained_hash_table.rs, matching.rs) of d_in[0..n): M, and Mq for a quarter budget.
 // Events: ev_mid is recorded between the chain structure (k_links / k_sort) and the walk.
 // The hash-sorted path does not represent the identity entries of the head table (head[h] = h at the start and for every
@@ -581,8 +718,8 @@ int launch_match_tables(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_i
                         bool redo_head = false, const Arrival* arr = nullptr, uint64_t quirk_end = 0, const SortInit* init = nullptr) {
     const uint32_t n32 = (uint32_t)n;
     const int aligned16 = ((reinterpret_cast<uintptr_t>(d_in) & 15) == 0) ? 1 : 0;
-    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
-    const bool has_q = cfg.use_quarter && cq;
+    const uint32_t cq = cfg_cq(cfg);
+    const bool has_q = cfg_has_q(cfg);
     if (cfg.use_quarter && cq == 0) HIPCHK(c, hipMemsetAsync(w.Mq, 0, (n + 64) * 4, st));
     // Positions that a write pattern around a sync flush left out of the chains or filed a byte late (ov.ns | ov.nh) are
     // candidates -- or missing ones -- for as long as they are inside the window: the epochs up to the one behind the last
@@ -642,7 +779,7 @@ int launch_match_tables(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_i
                 }
                 launch_sort(c, st, e_hi - e_lo, d_in, n32, ov, S, w.buckets, e_lo, e_lo == 0 ? init : nullptr);
                 if (e_lo == 0 && ev_mid) HIPCHK(c, hipEventRecord(ev_mid, st));  // (the stage clocks of such a call split at the first piece's sort)
-                launch_walk(c, st, d_in, n32, S, w, cfg, has_q, cq, aligned16, sg, ov, e_lo, e_hi - e_lo, match3_split(e_hi - e_lo, c->n_cu));
+                launch_walk(c, st, d_in, n32, S, w, cfg, aligned16, sg, ov, e_lo, e_hi - e_lo);
                 e_lo = e_hi;
             }
             return MI355_OK;
@@ -652,7 +789,7 @@ int launch_match_tables(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_i
         launch_sort(c, st, n_ep - e_sort, d_in, n32, ov, S, w.buckets, e_sort, e_first == 0 ? init : nullptr);
         if (ev_mid) HIPCHK(c, hipEventRecord(ev_mid, st));
         const uint32_t ne = n_ep - e_first;
-        launch_walk(c, st, d_in, n32, S, w, cfg, has_q, cq, aligned16, sg, ov, e_first, ne, match3_split(ne, c->n_cu));
+        launch_walk(c, st, d_in, n32, S, w, cfg, aligned16, sg, ov, e_first, ne);
     }
     return MI355_OK;
 }
@@ -715,15 +852,8 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
         return MI355_E_UNSUPPORTED;
     }
     ParseCfg cfg;
-    cfg.checks = o->max_hash_checks;
-    cfg.lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;  // deflate_state.rs:105
-    cfg.mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);  // lz77.rs:211-231
-    cfg.use_quarter = (cfg.mode == MODE_LAZY && cfg.lazy_lt > 32) ? 1 : 0;
-    if (cfg.mode == MODE_LAZY && cfg.lazy_lt < 3) {
-        c->err = "lazy_if_less_than < 3 with Lazy matching is not supported (SURVEY A.4 Q3)";
-        return MI355_E_UNSUPPORTED;
-    }
-    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
+    if (const int rc = parse_cfg(c, o, &cfg)) return rc;
+    const bool hashing = cfg_hashing(cfg);
     const bool zlib = o->wrapper == 1;
     const bool gzip = o->wrapper == 2;
     if (o->wrapper > 2 || (gzip && (!gz_hdr || gz_len == 0 || gz_len > 0xFFFF))) return MI355_E_ARG;
@@ -766,7 +896,7 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
     info.in_len = n;
 
     const uint32_t n32 = (uint32_t)n;
-    HashOverride ov = {0, 0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+    HashOverride ov = NO_HASH_OVERRIDE;
     uint64_t quirk_end = 0;  // (launch_match_tables)
     if (rewarm && !rewarm->empty() && hashing && n >= 2) {  // flush points that re-warm the hash (stages.h)
         uint8_t b01[2];
@@ -880,6 +1010,8 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
             if (cfg.mode != MODE_RLE && !(reuse && pass == 0 && !in_emit) && !(spec && in_emit))
                 hipLaunchKernelGGL(k_adv, dim3(cdiv(n, 1024)), dim3(256), 0, st, n32, w.M, Mq, cfg, w.adv, sg, 0u);
             const uint16_t* const steps = in_emit ? nullptr : w.adv;
+            const SegRange all{w.K0, Piece{0u, 0u, 1u}, d_in, n32, 0u, n32, 0u, sg, steps, w.levels[0].E, w.xs, w.fixlist, &c->d_sc->n_fix[0],
+                               w.scan_part, m == 1 ? w.tend : nullptr, m == 1 ? w.pb : nullptr};
             if (!spec) {
                 hipLaunchKernelGGL(k_seg_exit, dim3(cdiv(w.K0, 4)), dim3(256), 0, st, n32, w.K0, w.adv, w.levels[0].X, 0u);
                 // the table tree: wide levels as launches of their own, the levels of at most TOP_UNITS units -- up and down -- in one
@@ -924,28 +1056,14 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
                 }
                 hipLaunchKernelGGL((k_emit<0, false>), dim3(cdiv(w.K0, 4)), dim3(256), 0, st, d_in, n32, w.K0, w.M, Mq, cfg, w.adv,
                                    w.levels[0].E, w.tokbuf, w.cnt, 0u, n32, sg, (uint32_t*)nullptr, SpecFix{nullptr, nullptr, nullptr}, 0u, 0u);
-                if (!small_tail)
-                    hipLaunchKernelGGL(k_scan_a, dim3(cdiv(w.K0, 1024)), dim3(1024), 0, st, w.K0, w.cnt, w.scan_part, (const uint32_t*)nullptr,
-                                       (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
             } else {
-                // Every segment finds its entry itself (a run-up of SPEC_W positions in front of it) and says where it was left;
-                // k_scan_a checks the chain of entries and exits.
+                // Every segment finds its entry itself and says where it was left; k_scan_a checks the chain of entries and exits.
                 if (fill_aside) HIPCHK(c, hipStreamWaitEvent(st, c->ev_fill[1], 0));
-                const SpecFix fx{w.fixlist, w.badmap, &c->d_sc->n_fix[0]};
-                MI355_LAUNCH_EMIT(1, steps, dim3(cdiv(w.K0, 4)), st, d_in, n32, w.K0, w.M, Mq, cfg, steps,
-                                   w.levels[0].E, w.tokbuf, w.cnt, 0u, n32, sg, w.xs, fx, 0u, 0u);
-                // a handful of entries that did not check out (seams of pieces of different kinds, a short periodic stretch) are
-                // parsed again from where the segment before them was left; what is still wrong then fails the check below
                 // (a small one-shot call: check, repair, the final check, the scan and the block table are k_small_fix below)
-                if (!small_tail) {
-                    hipLaunchKernelGGL(k_spec_check, dim3(cdiv(w.K0, 256)), dim3(256), 0, st, w.K0, (const uint32_t*)w.levels[0].E,
-                                       (const uint32_t*)w.xs, w.badmap, w.fixlist, &c->d_sc->n_fix[0], 0u);
-                    MI355_LAUNCH_EMIT(2, steps, dim3(FIX_MAX / 4), st, d_in, n32, w.K0, w.M, Mq, cfg, steps,
-                                       w.levels[0].E, w.tokbuf, w.cnt, 0u, n32, sg, w.xs, fx, 0u, 0u);
-                }
-                if (!small_tail)
-                    hipLaunchKernelGGL(k_scan_a, dim3(cdiv(w.K0, 1024)), dim3(1024), 0, st, w.K0, w.cnt, w.scan_part,
-                                       (const uint32_t*)w.levels[0].E, (const uint32_t*)w.xs, &reinterpret_cast<DevState*>(c->d_sc)->spec_bad, 0u);
+                if (small_tail)
+                    launch_spec_emit(st, w, cfg, all);
+                else
+                    launch_spec_entries(c, st, w, cfg, all);
             }
             if (small_tail) {
                 // a small one-shot call: the check of the chain, the repair, the scan and the block table in one workgroup
@@ -960,12 +1078,10 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
                                        w.levels[0].E, w.tokbuf, w.cnt, sg, xs, w.badmap, w.fixlist, w.nb_max, sync_tail ? 1u : 0u,
                                        &reinterpret_cast<DevState*>(c->d_sc)->spec_bad, w.base, c->d_sc, w.tend, w.pb, w.bstart, w.q13, w.tab,
                                        (pass == 0 && speculate) ? 1u : 0u);
+                hipLaunchKernelGGL(k_compact, dim3(cdiv(w.K0, 4)), dim3(256), 0, st, w.K0, w.tokbuf, w.cnt, w.base, w.dtok, c->d_sc, 0u);
             } else {
-                hipLaunchKernelGGL(k_scan_b, dim3(cdiv(w.K0, 1024)), dim3(1024), 0, st, w.K0, w.cnt, w.scan_part, w.base, c->d_sc,
-                                   m == 1 ? w.tend : nullptr, m == 1 ? w.pb : nullptr, Piece{0u, 0u, 1u});
+                launch_token_scan(c, st, w, all, !spec);
             }
-            hipLaunchKernelGGL(k_compact, dim3(cdiv(w.K0, 4)), dim3(256), 0, st, w.K0, w.tokbuf, w.cnt, w.base,
-                               w.dtok, c->d_sc, 0u);
         } else {
             hipLaunchKernelGGL(k_scan_zero, dim3(1), dim3(64), 0, st, c->d_sc);
         }
@@ -998,22 +1114,8 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
         MI355_LAUNCH_PACK(nbg * PSPLIT, c->n_cu, st, d_in, n32, w.dtok, c->d_sc, w.hdr, w.plan, w.bstart,
                            w.q13, (uint32_t)o->compat, reinterpret_cast<uint32_t*>(d_out), w.tab, w.ll_freq, w.d_freq, 0u);
         HIPCHK(c, mark(5));
-        if (zlib) {
-            uint32_t nch = cdiv(n, ADLER_CHUNK);
-            if (nch) hipLaunchKernelGGL(k_adler_part, dim3(nch), dim3(256), 0, st, d_in, n32, c->d_sc);
-            hipLaunchKernelGGL(k_adler_fold, dim3(1), dim3(64), 0, st, n32, c->d_sc);
-            hipLaunchKernelGGL(k_zlib_frame, dim3(1), dim3(64), 0, st, c->d_sc, d_out, sync_tail ? 0u : 1u);
-        }
-        if (gzip) {
-            uint32_t nch = cdiv(n, CRC_CHUNK);
-            HIPCHK(c, hipMemcpyAsync(w.gz_hdr, gz_hdr, gz_len, hipMemcpyHostToDevice, st));
-            if (nch) {
-                hipLaunchKernelGGL(k_crc_part, dim3(cdiv(nch, 256)), dim3(256), 0, st, d_in, n32, w.crc_part);
-                hipLaunchKernelGGL(k_crc_fold, dim3(cdiv(nch, 256)), dim3(256), 0, st, n32, nch, w.crc_part, c->d_sc);
-            }
-            hipLaunchKernelGGL(k_gzip_frame, dim3(1), dim3(64), 0, st, c->d_sc, d_out, w.gz_hdr, (uint32_t)gz_len, n32,
-                               sync_tail ? 0u : 1u);
-        }
+        rc = launch_frame_tail(c, st, d_in, n, o->wrapper, w, gz_hdr, gz_len, d_out, !sync_tail);
+        if (rc) return rc;
         HIPCHK(c, mark(6));
         // (the scalars reach the host by a kernel that writes them into its page-locked memory)
         if (state_with_plan)
@@ -1047,14 +1149,7 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
     }
     const DevScalars& s = *c->h_sc;
     info.passes = passes;
-    info.n_tokens = s.T;
-    info.n_blocks = s.nb;
-    info.n_stored = s.n_stored;
-    info.n_fixed = s.n_fixed;
-    info.n_dynamic = s.n_dynamic;
-    info.q13_hits = s.q13_hits;
-    info.spec_repaired = 0;
-    for (uint32_t k = 0; k < PIECES_MAX; k++) info.spec_repaired += s.n_fix[k];
+    info_from_scalars(&info, s);
     c->pend_passes = passes;
     c->pend_clocks = clocks;
     if (!clocks) info.total_ms = host_ms;
@@ -1069,8 +1164,7 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
     c->last_nb = s.nb;
     c->last_T = s.T;
     c->last_bit_base = bit_base;
-    size_t total = (size_t)((s.total_bits + 7) / 8) + (zlib ? (sync_tail ? 2 : 6) : 0) +
-                   (gzip ? gz_len + (sync_tail ? 0 : 8) : 0);
+    const size_t total = stream_bytes(s.total_bits, o->wrapper, gz_len, sync_tail);
     c->last_crc = s.crc;
     *out_len = total;
     info.out_len = total;
@@ -1133,12 +1227,7 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
     };
     const bool two = c->host_streaming != 2;  // (2: the stages of a piece behind each other on one stream -- a measuring aid)
     ParseCfg cfg;
-    cfg.checks = o->max_hash_checks;
-    cfg.lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;
-    cfg.mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);
-    cfg.use_quarter = (cfg.mode == MODE_LAZY && cfg.lazy_lt > 32) ? 1 : 0;
-    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
-    if (!hashing || (cfg.mode == MODE_LAZY && cfg.lazy_lt < 3) || o->wrapper > 2 || o->flush != MI355_FLUSH_FINISH || c->live_shard ||
+    if (parse_cfg(c, o, &cfg) != MI355_OK || !cfg_hashing(cfg) || o->wrapper > 2 || o->flush != MI355_FLUSH_FINISH || c->live_shard ||
         c->spec_pause > 0 || ar.n < STREAMED_MIN_PIECES || n >= 0xFFFF0000ull)
         return MI355_OK;  // (not this way: *redo)
     const bool zlib = o->wrapper == 1, gzip = o->wrapper == 2;
@@ -1172,16 +1261,14 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
     c->pend_passes = 0;
     info.in_len = n;
     const uint32_t n32 = (uint32_t)n;
-    const HashOverride ov = {0, 0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+    const HashOverride& ov = NO_HASH_OVERRIDE;
     const int aligned16 = ((reinterpret_cast<uintptr_t>(d_in) & 15) == 0) ? 1 : 0;
-    const uint32_t cq = cfg.use_quarter ? (cfg.checks >> 2) : 0;
-    const bool has_q = cfg.use_quarter && cq;
     const uint64_t bit_base = zlib ? 16 : (gzip ? 8 * (uint64_t)gz_len : 0);
     const uint32_t* Mq = cfg.use_quarter ? w.Mq : nullptr;
     // the clears of the call beside the first piece's match stage (run_encode)
     HIPCHK(c, hipEventRecord(c->ev_fill[0], st));
     HIPCHK(c, hipEventRecord(c->ev[0][0], st));
-    if (cfg.use_quarter && cq == 0) HIPCHK(c, hipMemsetAsync(w.Mq, 0, (n + 64) * 4, st));
+    if (cfg.use_quarter && cfg_cq(cfg) == 0) HIPCHK(c, hipMemsetAsync(w.Mq, 0, (n + 64) * 4, st));
     uint16_t* S = w.sorted + WINDOW_SIZE;
     const uint32_t n_ep = (uint32_t)((n + WINDOW_SIZE - 1) / WINDOW_SIZE);
     const uint32_t spe = WINDOW_SIZE / SEG;  // segments per epoch
@@ -1201,7 +1288,7 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
         if (e_hi > e_lo) {
             launch_sort(c, st, e_hi - e_lo, d_in, n32, ov, S, w.buckets, e_lo);
             if (e_lo == 0) HIPCHK(c, hipEventRecord(c->ev[0][1], st));
-            launch_walk(c, st, d_in, n32, S, w, cfg, has_q, cq, aligned16, sg, ov, e_lo, e_hi - e_lo, match3_split(e_hi - e_lo, c->n_cu));
+            launch_walk(c, st, d_in, n32, S, w, cfg, aligned16, sg, ov, e_lo, e_hi - e_lo);
             if (last) HIPCHK(c, hipEventRecord(c->ev[0][2], st));
         }
         e_lo = e_hi;
@@ -1226,18 +1313,10 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
         if (ns) {
             const uint16_t* const steps = steps_in_emit(c, cfg, 1u) ? nullptr : w.adv;
             if (steps) hipLaunchKernelGGL(k_adv, dim3(ns), dim3(256), 0, sb, n32, w.M, Mq, cfg, w.adv, sg, seg_lo);
-            const SpecFix fx{w.fixlist + (size_t)2 * p * FIX_MAX, w.badmap, &c->d_sc->n_fix[p]};
-            MI355_LAUNCH_EMIT(1, steps, dim3(cdiv(ns, 4)), sb, d_in, n32, seg_hi, w.M, Mq, cfg, steps, w.levels[0].E,
-                               w.tokbuf, w.cnt, 0u, n32, sg, w.xs, fx, 0u, seg_lo);
-            hipLaunchKernelGGL(k_spec_check, dim3(cdiv(ns, 256)), dim3(256), 0, sb, seg_hi, (const uint32_t*)w.levels[0].E,
-                               (const uint32_t*)w.xs, w.badmap, fx.list, &c->d_sc->n_fix[p], seg_lo);
-            MI355_LAUNCH_EMIT(2, steps, dim3(FIX_MAX / 4), sb, d_in, n32, seg_hi, w.M, Mq, cfg, steps, w.levels[0].E,
-                               w.tokbuf, w.cnt, 0u, n32, sg, w.xs, fx, 0u, 0u);
-            uint32_t* part = w.scan_part + seg_lo / 1024 + 2 * p;
-            hipLaunchKernelGGL(k_scan_a, dim3(cdiv(ns, 1024)), dim3(1024), 0, sb, seg_hi, w.cnt, part, (const uint32_t*)w.levels[0].E,
-                               (const uint32_t*)w.xs, &reinterpret_cast<DevState*>(c->d_sc)->spec_bad, seg_lo);
-            hipLaunchKernelGGL(k_scan_b, dim3(cdiv(ns, 1024)), dim3(1024), 0, sb, seg_hi, w.cnt, part, w.base, c->d_sc, w.tend, w.pb, pc);
-            hipLaunchKernelGGL(k_compact, dim3(cdiv(ns, 4)), dim3(256), 0, sb, seg_hi, w.tokbuf, w.cnt, w.base, w.dtok, c->d_sc, seg_lo);
+            const SegRange r{seg_hi, pc, d_in, n32, 0u, n32, 0u, sg, steps, w.levels[0].E, w.xs, w.fixlist + (size_t)2 * p * FIX_MAX,
+                             &c->d_sc->n_fix[p], w.scan_part + seg_lo / 1024 + 2 * p, w.tend, w.pb};
+            launch_spec_entries(c, sb, w, cfg, r);
+            launch_token_scan(c, sb, w, r, false);
         } else {  // (an empty last piece cannot be: the last piece holds at least the 64 segments the one before it left)
             return MI355_OK;
         }
@@ -1258,21 +1337,8 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
         HIPCHK(c, hipEventRecord(c->ev_pack[p], sb));
         seg_lo = seg_hi;
     }
-    if (zlib) {
-        uint32_t nch = cdiv(n, ADLER_CHUNK);
-        if (nch) hipLaunchKernelGGL(k_adler_part, dim3(nch), dim3(256), 0, sb, d_in, n32, c->d_sc);
-        hipLaunchKernelGGL(k_adler_fold, dim3(1), dim3(64), 0, sb, n32, c->d_sc);
-        hipLaunchKernelGGL(k_zlib_frame, dim3(1), dim3(64), 0, sb, c->d_sc, d_out, 1u);
-    }
-    if (gzip) {
-        uint32_t nch = cdiv(n, CRC_CHUNK);
-        HIPCHK(c, hipMemcpyAsync(w.gz_hdr, gz_hdr, gz_len, hipMemcpyHostToDevice, sb));
-        if (nch) {
-            hipLaunchKernelGGL(k_crc_part, dim3(cdiv(nch, 256)), dim3(256), 0, sb, d_in, n32, w.crc_part);
-            hipLaunchKernelGGL(k_crc_fold, dim3(cdiv(nch, 256)), dim3(256), 0, sb, n32, nch, w.crc_part, c->d_sc);
-        }
-        hipLaunchKernelGGL(k_gzip_frame, dim3(1), dim3(64), 0, sb, c->d_sc, d_out, w.gz_hdr, (uint32_t)gz_len, n32, 1u);
-    }
+    rc = launch_frame_tail(c, sb, d_in, n, o->wrapper, w, gz_hdr, gz_len, d_out, true);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevState), hipMemcpyDeviceToHost, sb));
     // everything is queued; now hand the finished bytes over as the plans come in
     bool bad = false, q1 = false;
@@ -1291,13 +1357,9 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
         ht("plan", p);
         const DevState* hs = reinterpret_cast<const DevState*>(c->h_piece + (size_t)p * sizeof(DevState));
         if (hs->spec_bad || hs->sort_bad || hs->sc.ref_panic) bad = true;
-        if (p == 0 && hs->sc.b0_full) {  // quirk Q1 (run_encode q1_fires): the single pass deals with it
-            const uint32_t t = hs->sc.b0_last_tok;
-            const uint64_t tp = hs->sc.b0_last_pos;
-            const uint64_t lp = cfg.mode == MODE_LAZY ? tp + 1 : tp;
-            const uint64_t wpos = (cfg.mode == MODE_LAZY && !(t >> 16)) ? (((tp + 1) + 2 < n) ? tp + 2 : tp + 1) : tp + tok_cover(t);
-            if (lp < WINDOW_SIZE && wpos <= WINDOW_SIZE) bad = q1 = true;
-        }
+        uint64_t wpos = 0;
+        // quirk Q1 (run_encode q1_fires): the single pass deals with it
+        if (p == 0 && hs->sc.b0_full && q1_rewarm(hs->sc.b0_last_tok, hs->sc.b0_last_pos, cfg.mode, n, &wpos)) bad = q1 = true;
         if (bad || p + 1 == np) break;  // (the last piece's bytes go with the trailer, below)
         // whole bytes that are final: the byte the next block starts in is not
         uint64_t upto = (bit_base + hs->sc.total_bits) / 8;
@@ -1340,7 +1402,7 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
         c->reuse_tables = spec_off && !sort_off && !q1 && !s.ref_panic;
         return MI355_OK;  // *redo stays set
     }
-    const size_t total = (size_t)((s.total_bits + 7) / 8) + (zlib ? 6 : 0) + (gzip ? gz_len + 8 : 0);
+    const size_t total = stream_bytes(s.total_bits, o->wrapper, gz_len, false);
     *out_len = total;
     if (total > out_cap) {
         (void)hipStreamSynchronize(c->out_stream);
@@ -1374,13 +1436,7 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
     ht("out", 0);
     if (host_trace) fprintf(stderr, "[host]%s ms (%s)\n", htl.c_str(), by_threads ? "host threads" : (by_engine ? "copy engine" : "runtime"));
     info.passes = 1;
-    info.n_tokens = s.T;
-    info.n_blocks = s.nb;
-    info.n_stored = s.n_stored;
-    info.n_fixed = s.n_fixed;
-    info.n_dynamic = s.n_dynamic;
-    info.q13_hits = s.q13_hits;
-    for (uint32_t k = 0; k < PIECES_MAX; k++) info.spec_repaired += s.n_fix[k];
+    info_from_scalars(&info, s);
     info.out_len = total;
     c->last_crc = s.crc;
     c->last_plan = w.plan;  // (the block trace of mi355_deflate_last_blocks: the tables are the stream's, as in the single pass)
@@ -1891,12 +1947,8 @@ int mi355_adler32_device(mi355_deflate_ctx* c, const void* d_in, size_t n, uint3
     if (!adler || (!d_in && n) || n >= 0xFFFF0000ull) return MI355_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
-    uint32_t nch = cdiv(n, ADLER_CHUNK);
     HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    if (nch)
-        hipLaunchKernelGGL(k_adler_part, dim3(nch), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(d_in),
-                           (uint32_t)n, c->d_sc);
-    hipLaunchKernelGGL(k_adler_fold, dim3(1), dim3(64), 0, st, (uint32_t)n, c->d_sc);
+    launch_adler(c, st, reinterpret_cast<const uint8_t*>(d_in), n);
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     *adler = c->h_sc->adler;
@@ -1915,11 +1967,7 @@ int mi355_crc32_device(mi355_deflate_ctx* c, const void* d_in, size_t n, uint32_
     if (rc) return rc;
     uint32_t* part = reinterpret_cast<uint32_t*>(c->d_crc);
     HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    if (nch) {
-        hipLaunchKernelGGL(k_crc_part, dim3(cdiv(nch, 256)), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(d_in),
-                           (uint32_t)n, part);
-        hipLaunchKernelGGL(k_crc_fold, dim3(cdiv(nch, 256)), dim3(256), 0, st, (uint32_t)n, nch, part, c->d_sc);
-    }
+    launch_crc(c, st, reinterpret_cast<const uint8_t*>(d_in), n, part);
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     *crc = c->h_sc->crc;

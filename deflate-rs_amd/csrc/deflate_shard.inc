@@ -95,7 +95,7 @@ int shard_tables(mi355_shard* s, const HashOverride& ov, bool redo_head = false)
     const ParseCfg& cfg = s->cfg;
     const uint64_t n = s->n_ext;
     const uint32_t n32 = (uint32_t)n;
-    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
+    const bool hashing = cfg_hashing(cfg);
     s->tables_done = false;
     s->spec_ok = false;
     // (a range whose bytes are still arriving from the host on the copy stream: mi355_deflate_encode_multi; the second pass
@@ -165,36 +165,31 @@ int shard_exit_tables(mi355_shard* s) {
     return MI355_OK;
 }
 
+// The segments of the range as the parse helpers see them: positions relative to lo, the exits where k_scan_b writes next.
+SegRange shard_range(const mi355_shard* s) {
+    const Workspace& w = s->w;
+    // (the first segment has the range's history in front of it, unless the range begins the stream)
+    const uint32_t runup0 = s->lo >= SPEC_W ? 1u : 0u;
+    return SegRange{s->lv[0].count, Piece{0u, 0u, 1u}, s->d_ext, (uint32_t)(s->hi - s->lo), (uint32_t)s->lo, (uint32_t)s->n_ext, runup0, s->sg,
+                    s->steps_done ? w.adv : nullptr, s->lv[0].E, w.base, w.fixlist, &s->c->d_sc->n_fix[0], w.scan_part, nullptr, nullptr};
+}
+
 // The range parsed by speculation: tokens, their count, entry and exit -- and whether the chain inside the range held.
 int shard_spec(mi355_shard* s) {
     mi355_deflate_ctx* c = s->c;
     hipStream_t st = s->st;
     Workspace& w = s->w;
-    const uint32_t nr = (uint32_t)(s->hi - s->lo);
-    const uint32_t* Mq = s->cfg.use_quarter ? w.Mq : nullptr;
     const uint32_t K = s->lv[0].count;
     s->spec_ok = false;
     if (K == 0) return MI355_OK;
     HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    const SpecFix fx{w.fixlist, w.badmap, &c->d_sc->n_fix[0]};
-    // (the first segment has the range's history in front of it, unless the range begins the stream)
-    const uint32_t runup0 = s->lo >= SPEC_W ? 1u : 0u;
-    const uint16_t* const steps = s->steps_done ? w.adv : nullptr;
-    MI355_LAUNCH_EMIT(1, steps, dim3(cdiv(K, 4)), st, s->d_ext, nr, K, w.M, Mq, s->cfg, steps, s->lv[0].E, w.tokbuf,
-                       w.cnt, (uint32_t)s->lo, (uint32_t)s->n_ext, s->sg, w.base, fx, runup0, 0u);
-    hipLaunchKernelGGL(k_spec_check, dim3(cdiv(K, 256)), dim3(256), 0, st, K, (const uint32_t*)s->lv[0].E, (const uint32_t*)w.base,
-                       w.badmap, w.fixlist, &c->d_sc->n_fix[0], 0u);
-    MI355_LAUNCH_EMIT(2, steps, dim3(FIX_MAX / 4), st, s->d_ext, nr, K, w.M, Mq, s->cfg, steps, s->lv[0].E, w.tokbuf,
-                       w.cnt, (uint32_t)s->lo, (uint32_t)s->n_ext, s->sg, w.base, fx, 0u, 0u);
-    hipLaunchKernelGGL(k_scan_a, dim3(cdiv(K, 1024)), dim3(1024), 0, st, K, w.cnt, w.scan_part, (const uint32_t*)s->lv[0].E,
-                       (const uint32_t*)w.base, &reinterpret_cast<DevState*>(c->d_sc)->spec_bad, 0u);
+    const SegRange r = shard_range(s);
+    launch_spec_entries(c, st, w, s->cfg, r);
     // (entry of the first segment and exit of the last one travel with the scalars; the exits lie where k_scan_b writes next)
     DevState* const dst = reinterpret_cast<DevState*>(c->d_sc);
     HIPCHK(c, hipMemcpyAsync(&dst->pad[0], s->lv[0].E, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipMemcpyAsync(&dst->pad[1], w.base + (K - 1), sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_scan_b, dim3(cdiv(K, 1024)), dim3(1024), 0, st, K, w.cnt, w.scan_part, w.base, c->d_sc, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr, Piece{0u, 0u, 1u});
-    hipLaunchKernelGGL(k_compact, dim3(cdiv(K, 4)), dim3(256), 0, st, K, w.tokbuf, w.cnt, w.base, w.dtok, c->d_sc, 0u);
+    launch_token_scan(c, st, w, r, false);
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevState), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
@@ -236,15 +231,7 @@ int shard_emit(mi355_shard* s, uint64_t entry) {
     HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
     hipLaunchKernelGGL((k_emit<0, false>), dim3(cdiv(K, 4)), dim3(256), 0, st, s->d_ext, nr, K, w.M, Mq, s->cfg, w.adv, s->lv[0].E,
                        w.tokbuf, w.cnt, (uint32_t)s->lo, (uint32_t)s->n_ext, s->sg, (uint32_t*)nullptr, SpecFix{nullptr, nullptr, nullptr}, 0u, 0u);
-    if (K) {
-        hipLaunchKernelGGL(k_scan_a, dim3(cdiv(K, 1024)), dim3(1024), 0, st, K, w.cnt, w.scan_part, (const uint32_t*)nullptr,
-                           (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
-        hipLaunchKernelGGL(k_scan_b, dim3(cdiv(K, 1024)), dim3(1024), 0, st, K, w.cnt, w.scan_part, w.base, c->d_sc,
-                           (uint32_t*)nullptr, (uint32_t*)nullptr, Piece{0u, 0u, 1u});
-    } else {
-        hipLaunchKernelGGL(k_scan_zero, dim3(1), dim3(64), 0, st, c->d_sc);
-    }
-    hipLaunchKernelGGL(k_compact, dim3(cdiv(K, 4)), dim3(256), 0, st, K, w.tokbuf, w.cnt, w.base, w.dtok, c->d_sc, 0u);
+    launch_token_scan(c, st, w, shard_range(s), true);  // (K > 0: a range is not empty, shard_begin_at)
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     s->entry = entry;
@@ -267,9 +254,9 @@ int shard_begin_body(mi355_shard* s, const void* d_ext) {
         HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->w.seg_ends), (int)(uint32_t)n_ext, 1, s->st));
         s->sg = SegEnds{s->w.seg_ends, 1};
     }
-    HashOverride ov = {0, 0, 0, 0, 0, nullptr, 0, nullptr, 0, nullptr};
+    HashOverride ov = NO_HASH_OVERRIDE;
     s->quirk_end = 0;
-    if (n_quirks && cfg.mode != MODE_RLE && cfg.checks > 0) {
+    if (n_quirks && cfg_hashing(cfg)) {
         const size_t ns = s->skew.size(), nh = s->holes.size();
         if (ns) HIPCHK(c, hipMemcpyAsync(s->w.quirks, s->skew.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
         if (nh) HIPCHK(c, hipMemcpyAsync(s->w.quirks + ns, s->holes.data(), nh * sizeof(uint32_t), hipMemcpyHostToDevice, s->st));
@@ -280,7 +267,7 @@ int shard_begin_body(mi355_shard* s, const void* d_ext) {
         ov.hol = s->w.quirks + ns;
         s->quirk_end = quirk_reach(&s->skew, &s->holes);
     }
-    if ((!s->rewarm.empty() || s->q1_given) && cfg.mode != MODE_RLE && cfg.checks > 0 && n_ext >= 2) {
+    if ((!s->rewarm.empty() || s->q1_given) && cfg_hashing(cfg) && n_ext >= 2) {
         // (run_encode does the same for a stream's flush calls: the re-warmed hashes take the stream's first two bytes)
         const size_t at = s->skew.size() + s->holes.size(), nr = s->rewarm.size();
         uint8_t b01[2];
@@ -308,7 +295,7 @@ int shard_begin_body(mi355_shard* s, const void* d_ext) {
     // position 0 looks at its block 0 before anybody uses its exit table.  (A range that begins at a flush point inside the
     // first window does the same with the block that begins there -- only one block of a stream can fill inside the first
     // window, and if it lay before the flush point the stream's flush call has found it: q1_given.)
-    const bool hashing = cfg.mode != MODE_RLE && cfg.checks > 0;
+    const bool hashing = cfg_hashing(cfg);
     if (!rc && global_lo == 0 && (parse_lo == 0 || (s->from_flush && parse_lo < WINDOW_SIZE)) && !s->q1_given && hashing &&
         n_ext >= MAX_BUFFER_LENGTH) {
         rc = shard_emit(s, parse_lo);  // (nothing to do if the speculation held and entered the range right there)
@@ -323,16 +310,8 @@ int shard_begin_body(mi355_shard* s, const void* d_ext) {
                 uint64_t tp = 0;
                 HIPCHK(c, hipMemcpyAsync(&tp, s->d_cover, 8, hipMemcpyDeviceToHost, s->st));
                 HIPCHK(c, hipStreamSynchronize(s->st));
-                tp += parse_lo;
-                uint64_t lp, wpos;
-                if (cfg.mode == MODE_LAZY) {
-                    lp = tp + 1;
-                    wpos = (t >> 16) ? tp + tok_cover(t) : (((tp + 1) + 2 < n_global) ? tp + 2 : tp + 1);
-                } else {
-                    lp = tp;
-                    wpos = tp + tok_cover(t);
-                }
-                if (lp < WINDOW_SIZE && wpos <= WINDOW_SIZE) {
+                uint64_t wpos = 0;
+                if (q1_rewarm(t, tp + parse_lo, cfg.mode, n_global, &wpos)) {
                     uint8_t b01[2];
                     HIPCHK(c, hipMemcpy(b01, d_ext, 2, hipMemcpyDeviceToHost));
                     ov.on = 1;
@@ -400,11 +379,7 @@ static int shard_begin_at(mi355_deflate_ctx* c, const void* d_ext, size_t n_ext,
     if ((global_lo % WINDOW_SIZE) != 0) return MI355_E_ARG;  // window geometry must line up
     if (o->wrapper != 0 || o->flush != 0) return MI355_E_UNSUPPORTED;
     ParseCfg cfg;
-    cfg.checks = o->max_hash_checks;
-    cfg.lazy_lt = o->lazy_if_less_than < 32768 ? o->lazy_if_less_than : 32768;
-    cfg.mode = o->matching_type == 0 ? MODE_GREEDY : (o->max_hash_checks == 0 ? MODE_RLE : MODE_LAZY);
-    cfg.use_quarter = (cfg.mode == MODE_LAZY && cfg.lazy_lt > 32) ? 1 : 0;
-    if (cfg.mode == MODE_LAZY && cfg.lazy_lt < 3) return MI355_E_UNSUPPORTED;
+    if (const int rc = parse_cfg(c, o, &cfg)) return rc;
     if (c->live_shard) {
         c->err = "this context already holds a sharded encode between mi355_shard_begin and mi355_shard_end";
         return MI355_E_STATE;
