@@ -4,7 +4,9 @@
 // and the zlib frame.  Every batched kernel below runs the body of its single-call kernel; the arguments come from the item's
 // descriptor (BatchItem) instead of the launch.  A launch's grid is the items' workgroups back to back, and a workgroup finds its item
 // by a search over the stage's running sums (stages.h batch_item_of).  The stages that are one workgroup per call (k_small_fix,
-// k_plan, the zlib tail) are one workgroup per item.  DESIGN.md section 10.
+// k_plan, the zlib tail, the gzip tail) are one workgroup per item.  A gzip batch (mi355_deflate_encode_batch[_device]_gzip) adds
+// kb_crc, the CRC-32 of every item in one flat grid, and kb_gzip_tail, which writes the item's header and trailer with byte stores
+// after the pack (a header has any length, so an item's stream starts on any byte of a word).  DESIGN.md section 10.
 namespace mi355 {
 
 struct BatchItem {
@@ -12,7 +14,8 @@ struct BatchItem {
     uint32_t n, K0, nb_max;
     uint32_t q1_check;   // the item's first pass may fire Q1: k_small_fix stops its block stages (run_encode `speculate`)
     uint32_t out_words;  // mi355_deflate_bound_ex(n, wrapper, 0, 0) / 4: cleared by kb_block_hist (k_pack ORs its bits in)
-    uint32_t pad;
+    uint32_t bit_base;   // bits of the frame in front of the item's stream: 0 (raw), 16 (zlib), 8 * the header's bytes (gzip)
+    uint32_t gz_off, gz_len;  // gzip: the item's header in the set's header bytes (kb_gzip_tail)
     uint32_t *M, *Mq;
     uint16_t *adv, *S, *B;  // S: the sorted positions behind their pad epoch
     uint32_t *E0, *tokbuf, *cnt, *xs, *badmap, *fixlist, *base, *tend, *pb, *bstart, *q13, *dtok, *ll_freq, *d_freq, *seg_ends;
@@ -23,7 +26,7 @@ struct BatchItem {
     uint8_t* out;
 };
 // the stages with a grid of their own per item (a row of running sums each)
-enum : uint32_t { BS_SORT, BS_WALK, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_N };
+enum : uint32_t { BS_SORT, BS_WALK, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_CRC, BS_N };
 struct BatchArgs {
     const BatchItem* it;
     const uint32_t* pre;  // BS_N rows of n_items + 1 running sums of workgroups
@@ -124,10 +127,10 @@ __global__ __launch_bounds__(128) void kb_block_header(BatchArgs bat_) {
     k_block_header_body(local, &it.st->sc, it.ll_freq, it.d_freq, it.hdr, 0u);
 }
 
-__global__ __launch_bounds__(1024) void kb_plan(BatchArgs bat_, uint64_t bit_base, uint32_t compat) {
+__global__ __launch_bounds__(1024) void kb_plan(BatchArgs bat_, uint32_t compat) {
     __shared__ uint32_t s_red[16], s_flag[3];
     const BatchItem& it = bat_.it[blockIdx.x];
-    plan_blocks(s_red, s_flag, &it.st->sc, it.hdr, it.bstart, it.q13, it.plan, bit_base, compat, it.tab.sync,
+    plan_blocks(s_red, s_flag, &it.st->sc, it.hdr, it.bstart, it.q13, it.plan, (uint64_t)it.bit_base, compat, it.tab.sync,
                 reinterpret_cast<uint32_t*>(it.out), Piece{0u, 0u, 1u});
 }
 
@@ -167,6 +170,45 @@ __global__ __launch_bounds__(64) void kb_zlib_tail(BatchArgs bat_) {
     k_zlib_frame_body(0u, &it.st->sc, it.out, 1u);
 }
 
+// k_crc_part and k_crc_fold of an item in one kernel: a thread runs the table CRC over its CRC_CHUNK bytes (the body of k_crc_part),
+// multiplies it by x^(8 * bytes of the item behind the chunk) and the products are XOR-ed: over the wave by shuffles, over the
+// workgroup through LDS, then one atomicXor into the item's scalar (cleared by the item's kb_sort).  No per-chunk words in memory.
+__global__ __launch_bounds__(256) void kb_crc(BatchArgs bat_) {
+    __shared__ uint32_t s_wave[4];
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_CRC, local, count)];
+    const uint8_t* in = it.in;
+    const uint32_t n = it.n;
+#define BX_ local
+#include "body_k_crc_part.inc"
+#undef BX_
+    uint32_t v = 0;
+    if (mylen) {
+        const uint64_t after = n - (my0 + mylen);
+        v = ~crc;
+        if (after) v = crc_mulmod(crc_xpow8(after), v);
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v ^= __shfl_xor(v, off, 64);
+    if ((tid & 63) == 0) s_wave[tid >> 6] = v;
+    __syncthreads();
+    if (tid) return;
+    v = s_wave[0] ^ s_wave[1] ^ s_wave[2] ^ s_wave[3];
+    if (v) atomicXor(&it.st->sc.crc, v);
+}
+
+// k_gzip_frame of an item: its header from the set's header bytes, CRC-32 and length behind the stream
+__global__ __launch_bounds__(64) void kb_gzip_tail(BatchArgs bat_, const uint8_t* __restrict__ gz) {
+    const BatchItem& it = bat_.it[blockIdx.x];
+    DevScalars* sc = &it.st->sc;
+    uint8_t* out = it.out;
+    const uint8_t* hdr = gz + it.gz_off;
+    const uint32_t hdr_len = it.gz_len, in_len = it.n, trailer = 1u;
+#define BX_ 0u
+#include "body_k_gzip_frame.inc"
+#undef BX_
+}
+
 }  // namespace mi355
 
 namespace {
@@ -182,6 +224,18 @@ struct BatchView {
     size_t idx;  // in the caller's array
 };
 
+// The gzip headers of a batch (wrapper 2; n as n_hdrs of mi355_deflate_encode_batch_gzip): none for raw and zlib.
+struct BatchHeaders {
+    const mi355_gzip_header* h = nullptr;
+    size_t n = 0;
+    bool gzip = false;
+    mi355_gzip_header of(size_t i) const {  // the header of item i of the caller's array
+        if (!gzip) return mi355_gzip_header{nullptr, 0};
+        if (n == 0) return mi355_gzip_header{kBlankGzipHeader, sizeof kBlankGzipHeader};
+        return h[n == 1 ? 0 : i];
+    }
+};
+
 // Can the batched kernels take this item?  (Else: the one-input path, after the launch sets.)
 bool batch_takes(const ParseCfg& cfg, uint64_t n) {
     return MI355_SMALL_TAIL && cfg_hashing(cfg) && !(cfg.use_quarter && cfg_cq(cfg) == 0) && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
@@ -191,8 +245,8 @@ enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
 
 // One launch set over v[0..k): the kernels, one copy of the items' scalars back, one wait.  out_len / outcome per item.
 int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const mi355_deflate_opts* o, const ParseCfg& cfg,
-                     hipStream_t st, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
-    const bool zlib = o->wrapper == 1;
+                     hipStream_t st, const BatchHeaders& gz, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
+    const bool zlib = o->wrapper == 1, gzip = o->wrapper == 2;
     const uint32_t cq = cfg_cq(cfg);
     const bool has_q = cfg_has_q(cfg);
     // the items' workspaces, one behind the other in the context's one workspace
@@ -201,7 +255,20 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     int rc = ensure_ws(c, ws_off[k]);
     if (rc) return rc;
     const size_t pre_words = (size_t)BS_N * (k + 1);
-    const size_t desc_bytes = align_up(sizeof(BatchItem) * k + sizeof(uint32_t) * pre_words, 256);
+    // the set's header bytes behind the running sums, in the same copy: a header shared by neighbours (the blank one, one for all) once
+    const size_t gz_at = sizeof(BatchItem) * k + sizeof(uint32_t) * pre_words;
+    std::vector<uint32_t> gz_off(gzip ? k : 0, 0);
+    size_t gz_bytes = 0;
+    for (uint32_t i = 0; i < k && gzip; i++) {
+        const mi355_gzip_header h = gz.of(v[i].idx), prev = i ? gz.of(v[i - 1].idx) : mi355_gzip_header{nullptr, 0};
+        if (i && h.hdr == prev.hdr && h.hdr_len == prev.hdr_len) {
+            gz_off[i] = gz_off[i - 1];
+        } else {
+            gz_off[i] = (uint32_t)gz_bytes;
+            gz_bytes += h.hdr_len;
+        }
+    }
+    const size_t desc_bytes = align_up(gz_at + gz_bytes, 256);
     const size_t state_bytes = sizeof(DevState) * k;
     rc = ensure_buf(c, &c->b_dev, &c->b_dev_cap, desc_bytes + state_bytes);
     if (rc) return rc;
@@ -214,6 +281,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     }
     BatchItem* hit = reinterpret_cast<BatchItem*>(c->b_host);
     uint32_t* hpre = reinterpret_cast<uint32_t*>(c->b_host + sizeof(BatchItem) * k);
+    uint8_t* hgz = c->b_host + gz_at;
     DevState* hst = reinterpret_cast<DevState*>(c->b_host + desc_bytes);
     DevState* dst = reinterpret_cast<DevState*>(c->b_dev + desc_bytes);
     // the walk's parts per epoch: as launch_walk cuts the epochs of one call, for all epochs of the set
@@ -234,6 +302,14 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         d.nb_max = w.nb_max;
         d.q1_check = v[i].n >= MAX_BUFFER_LENGTH ? 1u : 0u;
         d.out_words = (uint32_t)(v[i].need / 4);
+        d.bit_base = zlib ? 16u : 0u;
+        if (gzip) {
+            const mi355_gzip_header h = gz.of(v[i].idx);
+            d.bit_base = 8u * (uint32_t)h.hdr_len;
+            d.gz_off = gz_off[i];
+            d.gz_len = (uint32_t)h.hdr_len;
+            if (i == 0 || gz_off[i] != gz_off[i - 1]) memcpy(hgz + gz_off[i], h.hdr, h.hdr_len);
+        }
         d.M = w.M;
         d.Mq = w.Mq;
         d.adv = w.adv;
@@ -261,7 +337,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         d.out = v[i].d_out;
         const uint64_t n_ep = (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
         const uint64_t wg[BS_N] = {n_ep, n_ep * split, cdiv(v[i].n, ADV_TILE), cdiv(w.K0, 4), cdiv(w.K0, 4), (uint64_t)w.nb_max * PSPLIT,
-                                   w.nb_max, (uint64_t)w.nb_max * PSPLIT, cdiv(v[i].n, ADLER_CHUNK)};
+                                   w.nb_max, (uint64_t)w.nb_max * PSPLIT, cdiv(v[i].n, ADLER_CHUNK), gzip ? cdiv(v[i].n, 256 * CRC_CHUNK) : 0u};
         for (uint32_t s = 0; s < BS_N; s++) {
             const uint64_t t = (uint64_t)hpre[(size_t)s * (k + 1) + i] + wg[s];
             if (t > 0x7fffffffull) return MI355_E_ARG;  // (a launch set of at most 256 MiB of input is far below this)
@@ -270,7 +346,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     }
     auto total = [&](uint32_t s) { return hpre[(size_t)s * (k + 1) + k]; };
     const BatchArgs a{reinterpret_cast<const BatchItem*>(c->b_dev), reinterpret_cast<const uint32_t*>(c->b_dev + sizeof(BatchItem) * k), k};
-    HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, sizeof(BatchItem) * k + sizeof(uint32_t) * pre_words, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, gz_at + gz_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemsetAsync(dst, 0, state_bytes, st));  // (the flags behind the scalars: k_sort clears the scalars themselves)
     // ---- match table ----
     if (c->sort_mode == 1)
@@ -304,7 +380,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     else
         hipLaunchKernelGGL(kb_block_hist<256>, dim3(total(BS_HIST)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(kb_block_header, dim3(total(BS_HEADER)), dim3(128), 0, st, a);
-    hipLaunchKernelGGL(kb_plan, dim3(k), dim3(1024), 0, st, a, (uint64_t)(zlib ? 16 : 0), (uint32_t)o->compat);
+    hipLaunchKernelGGL(kb_plan, dim3(k), dim3(1024), 0, st, a, (uint32_t)o->compat);
     if (total(BS_PACK) <= cus)
         hipLaunchKernelGGL(kb_pack<PKT_SMALL>, dim3(total(BS_PACK)), dim3(PKT_SMALL), 0, st, a, (uint32_t)o->compat);
     else
@@ -312,6 +388,10 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     if (zlib) {
         hipLaunchKernelGGL(kb_adler_part, dim3(total(BS_ADLER)), dim3(256), 0, st, a);
         hipLaunchKernelGGL(kb_zlib_tail, dim3(k), dim3(64), 0, st, a);
+    }
+    if (gzip) {
+        hipLaunchKernelGGL(kb_crc, dim3(total(BS_CRC)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(kb_gzip_tail, dim3(k), dim3(64), 0, st, a, static_cast<const uint8_t*>(c->b_dev + gz_at));
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hst, dst, state_bytes, hipMemcpyDeviceToHost, st));
@@ -324,7 +404,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             return MI355_E_HIP;
         }
         sort_fell_back(c);
-        return batch_launch_set(c, v, k, o, cfg, st, out_len, outcome, sums);
+        return batch_launch_set(c, v, k, o, cfg, st, gz, out_len, outcome, sums);
     }
     for (uint32_t i = 0; i < k; i++) {
         const DevScalars& s = hst[i].sc;
@@ -338,7 +418,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             outcome[i] = BO_PANIC;
         else {
             outcome[i] = BO_OK;
-            out_len[i] = stream_bytes(s.total_bits, o->wrapper, 0, false);
+            out_len[i] = stream_bytes(s.total_bits, o->wrapper, gz.of(v[i].idx).hdr_len, false);
             sums->T += s.T;
             sums->nb += s.nb;
             sums->n_stored += s.n_stored;
@@ -352,8 +432,9 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
 
 // The whole batch: launch sets over the items the batched kernels take, then the others one by one through the one-input path.
 // host: the items' buffers are the caller's host memory (gathered into the context's device staging per launch set).
+// gz: the items' gzip headers when o->wrapper is 2 (the _gzip entries), else none.
 int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, hipStream_t st, bool host,
-              void* hip_stream) {
+              void* hip_stream, const BatchHeaders& gz) {
     const auto t0 = std::chrono::steady_clock::now();
     if (c->live_shard) {
         c->err = "this context holds a sharded encode between mi355_shard_begin and mi355_shard_end";
@@ -376,7 +457,7 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
     for (size_t i = 0; i < n_items; i++) {
         mi355_batch_item& it = items[i];
         bi.in_len += it.in_len;
-        const size_t need = mi355_deflate_bound_ex(it.in_len, o->wrapper, 0, 0);
+        const size_t need = mi355_deflate_bound_ex(it.in_len, o->wrapper, gz.of(i).hdr_len, 0);
         it.out_len = 0;
         it.status = MI355_OK;
         if (it.out_cap < need) {
@@ -393,8 +474,10 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
     std::vector<BatchOutcome> outcome;
     for (size_t s0 = 0; s0 < v.size();) {
         size_t s1 = s0 + 1;
-        uint64_t bytes = v[s0].n;
-        while (s1 < v.size() && s1 - s0 < BATCH_ITEMS_MAX && bytes + v[s1].n <= c->batch_bytes) bytes += v[s1++].n;
+        // (a gzip item counts with its header, which travels with the set's descriptors)
+        auto set_bytes = [&](const BatchView& b) { return b.n + gz.of(b.idx).hdr_len; };
+        uint64_t bytes = set_bytes(v[s0]);
+        while (s1 < v.size() && s1 - s0 < BATCH_ITEMS_MAX && bytes + set_bytes(v[s1]) <= c->batch_bytes) bytes += set_bytes(v[s1++]);
         const uint32_t k = (uint32_t)(s1 - s0);
         BatchView* sv = v.data() + s0;
         std::vector<BatchView> staged;
@@ -418,7 +501,7 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
         }
         out_len.assign(k, 0);
         outcome.assign(k, BO_OK);
-        const int rc = batch_launch_set(c, sv, k, o, cfg, st, out_len.data(), outcome.data(), &sums);
+        const int rc = batch_launch_set(c, sv, k, o, cfg, st, gz, out_len.data(), outcome.data(), &sums);
         if (rc) return rc;
         bi.sub_batches++;
         for (uint32_t i = 0; i < k; i++) {
@@ -454,7 +537,13 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
         mi355_batch_item& it = items[i];
         size_t len = 0;
         int rc;
-        if (host)
+        const mi355_gzip_header h = gz.of(i);
+        if (gz.gzip && host)
+            rc = mi355_deflate_encode_gzip(c, reinterpret_cast<const uint8_t*>(it.in), it.in_len, o, h.hdr, h.hdr_len,
+                                           reinterpret_cast<uint8_t*>(it.out), it.out_cap, &len);
+        else if (gz.gzip)
+            rc = mi355_deflate_encode_device_gzip(c, it.in, it.in_len, o, h.hdr, h.hdr_len, it.out, it.out_cap, &len, hip_stream);
+        else if (host)
             rc = mi355_deflate_encode(c, reinterpret_cast<const uint8_t*>(it.in), it.in_len, o, reinterpret_cast<uint8_t*>(it.out),
                                       it.out_cap, &len);
         else
@@ -501,11 +590,23 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
 }
 
 // the checks of the call itself (nothing is written to an item when one fails)
-int batch_args_ok(mi355_deflate_ctx* c, const mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, bool device) {
+int batch_args_ok(mi355_deflate_ctx* c, const mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, bool device,
+                  const BatchHeaders& gz) {
     if (!o || (!items && n_items)) return MI355_E_ARG;
-    if (o->wrapper > 1) {
-        c->err = "batched encode: wrapper 0 (raw) or 1 (zlib) only";
+    if (o->wrapper > 1 && !gz.gzip) {
+        c->err = "batched encode: wrapper 0 (raw) or 1 (zlib) only; gzip has the _gzip entries";
         return MI355_E_ARG;
+    }
+    if (gz.gzip) {  // (the rule of the single gzip call, run_encode)
+        if ((gz.n && !gz.h) || (gz.n > 1 && gz.n != n_items)) {
+            c->err = "batched gzip encode: n_hdrs is 0 (blank header), 1 (one for all) or n_items";
+            return MI355_E_ARG;
+        }
+        for (size_t i = 0; i < gz.n; i++)
+            if (!gz.h[i].hdr || gz.h[i].hdr_len == 0 || gz.h[i].hdr_len > 0xFFFF) {
+                c->err = "batched gzip encode: a header of 1 .. 65535 bytes per entry";
+                return MI355_E_ARG;
+            }
     }
     if (o->flush != MI355_FLUSH_FINISH) {
         c->err = "batched encode: MI355_FLUSH_FINISH only";
@@ -529,9 +630,9 @@ int mi355_deflate_encode_batch(mi355_deflate_ctx* c, mi355_batch_item* items, si
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    int rc = batch_args_ok(c, items, n_items, opts, false);
+    int rc = batch_args_ok(c, items, n_items, opts, false, BatchHeaders{});
     if (rc) return rc;
-    return run_batch(c, items, n_items, opts, c->own_stream, true, nullptr);
+    return run_batch(c, items, n_items, opts, c->own_stream, true, nullptr, BatchHeaders{});
 }
 
 int mi355_deflate_encode_batch_device(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
@@ -539,10 +640,39 @@ int mi355_deflate_encode_batch_device(mi355_deflate_ctx* c, mi355_batch_item* it
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    int rc = batch_args_ok(c, items, n_items, opts, true);
+    int rc = batch_args_ok(c, items, n_items, opts, true, BatchHeaders{});
     if (rc) return rc;
     hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
-    return run_batch(c, items, n_items, opts, st, false, hip_stream);
+    return run_batch(c, items, n_items, opts, st, false, hip_stream, BatchHeaders{});
+}
+
+int mi355_deflate_encode_batch_gzip(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
+                                    const mi355_gzip_header* hdrs, size_t n_hdrs) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    if (!opts) return MI355_E_ARG;
+    mi355_deflate_opts o = *opts;
+    o.wrapper = 2;
+    const BatchHeaders gz{hdrs, n_hdrs, true};
+    int rc = batch_args_ok(c, items, n_items, &o, false, gz);
+    if (rc) return rc;
+    return run_batch(c, items, n_items, &o, c->own_stream, true, nullptr, gz);
+}
+
+int mi355_deflate_encode_batch_device_gzip(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
+                                           const mi355_gzip_header* hdrs, size_t n_hdrs, void* hip_stream) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    if (!opts) return MI355_E_ARG;
+    mi355_deflate_opts o = *opts;
+    o.wrapper = 2;
+    const BatchHeaders gz{hdrs, n_hdrs, true};
+    int rc = batch_args_ok(c, items, n_items, &o, true, gz);
+    if (rc) return rc;
+    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    return run_batch(c, items, n_items, &o, st, false, hip_stream, gz);
 }
 
 int mi355_deflate_last_batch_info(mi355_deflate_ctx* c, mi355_batch_info* info) {

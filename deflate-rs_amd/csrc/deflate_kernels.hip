@@ -3480,7 +3480,8 @@ __global__ void k_zlib_frame(DevScalars* sc, uint8_t* out, uint32_t trailer) {
 // reads its piece bank-conflict free (row stride 33 words).  k_crc_fold: CRCs are linear in the
 // sense of zlib's crc32_combine, crc(A||B) = x^(8|B|) * crc(A) + crc(B) over GF(2)[x] mod P, so
 // crc(input) = sum_i x^(8 * bytes after chunk i) * crc(chunk_i): every thread raises its own factor
-// by squaring and the products are XOR-ed together.
+// by squaring and the products are XOR-ed together.  The batch runs both in one kernel per launch set
+// (kb_crc, deflate_batch.inc) over the same body text (body_k_crc_part.inc, body_k_gzip_frame.inc).
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t CRC_CHUNK = 512;   // bytes per thread
 constexpr uint32_t CRC_PIECE = 128;   // bytes per thread per staging round
@@ -3510,62 +3511,9 @@ __device__ uint32_t crc_xpow8(uint64_t nbytes) {
 }
 
 __global__ __launch_bounds__(256) void k_crc_part(const uint8_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ part) {
-    __shared__ uint32_t T[4][256];
-    __shared__ uint32_t stage[256 * 33];
-    const uint32_t tid = threadIdx.x;
-    {
-        uint32_t c = tid;
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? CRC_POLY : 0u);
-        T[0][tid] = c;
-    }
-    __syncthreads();
-    for (int t = 1; t < 4; t++) {
-        uint32_t v = T[t - 1][tid];
-        T[t][tid] = (v >> 8) ^ T[0][v & 0xff];
-        __syncthreads();
-    }
-    const uint64_t tile = (uint64_t)blockIdx.x * 256 * CRC_CHUNK;
-    const uint64_t my0 = tile + (uint64_t)tid * CRC_CHUNK;
-    const uint32_t mylen = my0 >= n ? 0u : (n - my0 < CRC_CHUNK ? (uint32_t)(n - my0) : CRC_CHUNK);
-    const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-    uint32_t crc = 0xFFFFFFFFu;
-    for (uint32_t piece = 0; piece < CRC_CHUNK / CRC_PIECE; piece++) {
-        // stage: lane j of round r loads 16 bytes of chunk (r * 32 + j / 8), part j % 8
-        for (uint32_t r = 0; r < 8; r++) {
-            const uint32_t c = r * 32 + tid / 8, part16 = tid % 8;
-            const uint64_t g = tile + (uint64_t)c * CRC_CHUNK + piece * CRC_PIECE + part16 * 16;
-            uint32_t v[4] = {0, 0, 0, 0};
-            if (g + 16 <= n && aligned) {
-                const uint4 q = *reinterpret_cast<const uint4*>(in + g);
-                v[0] = q.x;
-                v[1] = q.y;
-                v[2] = q.z;
-                v[3] = q.w;
-            } else {
-                for (uint32_t b = 0; b < 16; b++)
-                    if (g + b < n) v[b >> 2] |= (uint32_t)in[g + b] << (8 * (b & 3));
-            }
-            uint32_t* dst = stage + c * 33 + part16 * 4;
-            dst[0] = v[0];
-            dst[1] = v[1];
-            dst[2] = v[2];
-            dst[3] = v[3];
-        }
-        __syncthreads();
-        const uint32_t done = piece * CRC_PIECE;
-        const uint32_t here = mylen > done ? (mylen - done < CRC_PIECE ? mylen - done : CRC_PIECE) : 0u;
-        const uint32_t* src = stage + tid * 33;
-        uint32_t w = 0;
-        for (; w * 4 + 4 <= here; w++) {
-            crc ^= src[w];
-            crc = T[3][crc & 0xff] ^ T[2][(crc >> 8) & 0xff] ^ T[1][(crc >> 16) & 0xff] ^ T[0][crc >> 24];
-        }
-        for (uint32_t b = w * 4; b < here; b++) {
-            const uint32_t d = (src[b >> 2] >> (8 * (b & 3))) & 0xff;
-            crc = T[0][(crc ^ d) & 0xff] ^ (crc >> 8);
-        }
-        __syncthreads();
-    }
+#define BX_ blockIdx.x
+#include "body_k_crc_part.inc"
+#undef BX_
     const uint64_t idx = (uint64_t)blockIdx.x * 256 + tid;
     if (mylen) part[idx] = ~crc;
 }
@@ -3589,14 +3537,9 @@ __global__ __launch_bounds__(256) void k_crc_fold(uint32_t n, uint32_t nchunks, 
 // stream CRC-32 and the input length mod 2^32, both little endian.
 __global__ void k_gzip_frame(DevScalars* sc, uint8_t* out, const uint8_t* hdr, uint32_t hdr_len, uint32_t in_len,
                              uint32_t trailer) {
-    if (blockIdx.x) return;
-    for (uint32_t i = threadIdx.x; i < hdr_len; i += blockDim.x) out[i] = hdr[i];
-    if (threadIdx.x || !trailer) return;
-    uint64_t nbytes = (sc->total_bits + 7) / 8;
-    uint8_t* t = out + hdr_len + nbytes;
-    uint32_t c = sc->crc;
-    for (int k = 0; k < 4; k++) t[k] = (uint8_t)(c >> (8 * k));
-    for (int k = 0; k < 4; k++) t[4 + k] = (uint8_t)(in_len >> (8 * k));
+#define BX_ blockIdx.x
+#include "body_k_gzip_frame.inc"
+#undef BX_
 }
 
 }  // namespace mi355

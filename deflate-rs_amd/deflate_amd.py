@@ -105,6 +105,11 @@ class BatchItem(C.Structure):
                 ("out_len", C.c_size_t), ("status", C.c_int)]
 
 
+class GzipHeader(C.Structure):
+    """mi355_gzip_header"""
+    _fields_ = [("hdr", C.c_char_p), ("hdr_len", C.c_size_t)]
+
+
 class BatchInfo(C.Structure):
     """mi355_batch_info"""
     _fields_ = [("n_items", C.c_uint64), ("in_len", C.c_uint64), ("out_len", C.c_uint64), ("n_batched", C.c_uint32),
@@ -206,6 +211,10 @@ def load():
     L.mi355_deflate_encode_batch.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts)]
     L.mi355_deflate_encode_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts), C.c_void_p]
     L.mi355_deflate_last_batch_info.argtypes = [C.c_void_p, C.POINTER(BatchInfo)]
+    L.mi355_deflate_encode_batch_gzip.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
+                                                  C.POINTER(GzipHeader), C.c_size_t]
+    L.mi355_deflate_encode_batch_device_gzip.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
+                                                         C.POINTER(GzipHeader), C.c_size_t, C.c_void_p]
     _lib = L
     return L
 
@@ -229,6 +238,7 @@ EXPORTED = [
     "mi355_multi_layout", "mi355_deflate_encode_multi", "mi355_deflate_encode_multi_device", "mi355_multi_last_trace",
     "mi355_multi_stitch_info",
     "mi355_deflate_encode_batch", "mi355_deflate_encode_batch_device", "mi355_deflate_last_batch_info",
+    "mi355_deflate_encode_batch_gzip", "mi355_deflate_encode_batch_device_gzip",
 ]
 
 
@@ -389,6 +399,76 @@ class Context:
             self._batch_error(rc, items[: len(ins_pl)])
         return outs, [items[k].out_len for k in range(len(ins_pl))], [items[k].status for k in range(len(ins_pl))]
 
+    @staticmethod
+    def _gzip_headers(headers, n_items):
+        """headers (None, one bytes, or a list as long as the batch) as (the GzipHeader array or None, n_hdrs, the bytes kept alive,
+        item i's header length)"""
+        if headers is None:
+            return None, 0, [], [len(BLANK_GZIP_HEADER)] * n_items
+        one = isinstance(headers, (bytes, bytearray, memoryview))
+        hs = [bytes(headers)] if one else [bytes(h) for h in headers]
+        if not one and len(hs) != n_items:
+            raise ValueError("headers: None, one bytes, or one per item (%d for %d items)" % (len(hs), n_items))
+        arr = (GzipHeader * max(len(hs), 1))()
+        for k, h in enumerate(hs):
+            arr[k].hdr = h
+            arr[k].hdr_len = len(h)
+        return arr, len(hs), hs, [len(hs[0 if one else k]) for k in range(n_items)]
+
+    def encode_batch_gzip(self, datas, options=Compression.Default, headers=None, compat=0):
+        """Many host inputs in one batched call, each a gzip member (mi355_deflate_encode_batch_gzip); a list of bytes, item i's
+        exactly what encode_gzip(datas[i], options, header_i) gives.  headers: None (the blank header), one bytes for all, or a
+        list as long as the batch (GzBuilder::into_header() bytes, e.g. gzip_header()).  Raises DeflateError naming the first
+        failing index."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(2, compat, 0)
+        datas = [bytes(d) for d in datas]
+        arr, n_hdrs, keep, hlen = self._gzip_headers(headers, len(datas))
+        items = (BatchItem * max(len(datas), 1))()
+        outs = []
+        for k, d in enumerate(datas):
+            cap = L.mi355_deflate_bound_ex(len(d), 2, hlen[k], 0)
+            out = (C.c_uint8 * max(cap, 1))()
+            outs.append(out)
+            items[k].in_ = C.cast(C.c_char_p(d), C.c_void_p) if d else C.c_void_p(0)
+            items[k].in_len = len(d)
+            items[k].out = C.cast(out, C.c_void_p)
+            items[k].out_cap = cap
+        rc = L.mi355_deflate_encode_batch_gzip(self._h, items, len(datas), C.byref(o), arr, n_hdrs)
+        if rc != OK:
+            self._batch_error(rc, items[: len(datas)])
+        return [bytes(memoryview(outs[k])[: items[k].out_len]) for k in range(len(datas))]
+
+    def encode_batch_device_gzip(self, ins, outs=None, options=Compression.Default, headers=None, compat=0, stream=0, check=True):
+        """Device inputs in one batched call, each a gzip member (mi355_deflate_encode_batch_device_gzip).  ins / outs / the
+        return value as encode_batch_device (outs None: uint8 tensors of mi355_deflate_bound_ex(n, 2, len(header_i), 0) bytes);
+        headers as encode_batch_gzip (host bytes)."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(2, compat, 0)
+
+        def ptr_len(x):
+            if isinstance(x, tuple):
+                return int(x[0]), int(x[1])
+            return int(x.data_ptr()), int(x.numel() * x.element_size())
+        ins_pl = [ptr_len(x) for x in ins]
+        arr, n_hdrs, keep, hlen = self._gzip_headers(headers, len(ins_pl))
+        if outs is None:
+            import torch
+            dev = ins[0].device if ins and not isinstance(ins[0], tuple) else torch.device("cuda", 0)
+            outs = [torch.empty(L.mi355_deflate_bound_ex(n, 2, hlen[k], 0), dtype=torch.uint8, device=dev)
+                    for k, (_, n) in enumerate(ins_pl)]
+        outs_pl = [ptr_len(x) for x in outs]
+        items = (BatchItem * max(len(ins_pl), 1))()
+        for k, ((ip, n), (op, cap)) in enumerate(zip(ins_pl, outs_pl)):
+            items[k].in_ = C.c_void_p(ip if n else 0)
+            items[k].in_len = n
+            items[k].out = C.c_void_p(op)
+            items[k].out_cap = cap
+        rc = L.mi355_deflate_encode_batch_device_gzip(self._h, items, len(ins_pl), C.byref(o), arr, n_hdrs, C.c_void_p(stream))
+        if rc != OK and check:
+            self._batch_error(rc, items[: len(ins_pl)])
+        return outs, [items[k].out_len for k in range(len(ins_pl))], [items[k].status for k in range(len(ins_pl))]
+
     def batch_info(self):
         """mi355_deflate_last_batch_info as a dict"""
         i = BatchInfo()
@@ -501,6 +581,15 @@ def deflate_bytes_gzip_conf(data, options, header=None, ctx=None):
 def deflate_bytes_gzip(data, ctx=None):
     """src/lib.rs:283-285"""
     return deflate_bytes_gzip_conf(data, Compression.Default, None, ctx)
+
+
+def deflate_bytes_gzip_batch_conf(datas, options, headers=None, ctx=None):
+    """deflate_bytes_gzip_conf of every input (src/lib.rs:242-267), in one batch; headers: None, one bytes, or one per input"""
+    return (ctx or default_context()).encode_batch_gzip(datas, options, headers)
+
+
+def deflate_bytes_gzip_batch(datas, ctx=None):
+    return deflate_bytes_gzip_batch_conf(datas, Compression.Default, None, ctx)
 
 
 # ---- the reference's Write encoders (src/writer.rs) ---------------------------------------------

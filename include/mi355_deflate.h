@@ -279,6 +279,35 @@ int mi355_deflate_encode_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* 
                                       const mi355_deflate_opts* opts, void* hip_stream);
 int mi355_deflate_last_batch_info(mi355_deflate_ctx* ctx, mi355_batch_info* info);
 
+/* The gzip forms of the batch (cargo feature "gzip"): every item is one gzip member with a header of its own, i.e.
+ *   item i = deflate_bytes_gzip_conf(input_i, options, builder_i)   src/lib.rs:242-267
+ * and byte for byte what mi355_deflate_encode_gzip gives for that item alone with the same opts and its header (whatever
+ * the other items, their order, their number or the way the batch is cut into launch sets).  opts->wrapper is taken as 2
+ * whatever it holds, as the single _gzip entries do; mi355_deflate_encode_batch[_device] itself keeps answering
+ * MI355_E_ARG to wrapper 2.
+ * hdrs[i].hdr = the bytes GzBuilder::into_header() returned for item i (host memory for both entries):
+ *   n_hdrs == 0        every item gets the blank header, GzBuilder::new() (hdrs is not read)
+ *   n_hdrs == 1        all items share hdrs[0]
+ *   n_hdrs == n_items  item i gets hdrs[i]
+ * Any other n_hdrs, a NULL hdrs with n_hdrs > 0, or an entry with a NULL pointer, length 0 or a length above 0xFFFF is
+ * MI355_E_ARG and writes no item; the other errors of the call are those of mi355_deflate_encode_batch.
+ * An item needs out_cap >= mi355_deflate_bound_ex(in_len, 2, hdr_len_i, 0); a shorter one gets MI355_E_OUT_TOO_SMALL and
+ * that size in out_len, the other items undisturbed.  The items the batched kernels take are those of the raw / zlib
+ * batch: CRC-32, header and trailer are written by the launches of the set (one more kernel for the CRC-32, one for the
+ * frame); the others go through mi355_deflate_encode_gzip / _device_gzip with their own header.
+ * Return value, mi355_deflate_last_batch_info, mi355_deflate_last_info and mi355_deflate_last_blocks: as after
+ * mi355_deflate_encode_batch[_device]. */
+typedef struct {
+    const uint8_t* hdr; /* host memory */
+    size_t hdr_len;     /* 1 .. 0xFFFF */
+} mi355_gzip_header;
+
+int mi355_deflate_encode_batch_gzip(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                                    const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs);
+int mi355_deflate_encode_batch_device_gzip(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                                           const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs,
+                                           void* hip_stream);
+
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
  * [parse_lo, parse_hi) (buffer coordinates; parse_lo = 32768 of history except on the first rank,

@@ -3,8 +3,11 @@
 Device-resident inputs, Default and Fast.  For each workload: (a) a loop of mi355_deflate_encode_device over the items, (b) one
 mi355_deflate_encode_batch_device call, (c) one mi355_deflate_encode_device call on the concatenation of the same bytes (other
 output bytes: the throughput ceiling, a yardstick only).  Every shape is warmed up before its timed window; every timed call
-ends in a synchronise.  Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--out FILE]"""
+ends in a synchronise.  --wrapper 1 / 2 times the same workloads with zlib / gzip framing (2: the blank header, the loop over
+mi355_deflate_encode_device_gzip, the batch through mi355_deflate_encode_batch_device_gzip; profiles/batch_bench_gzip.json holds
+a run of 2 and of 1 from one session).  Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--wrapper W] [--out FILE]"""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -46,31 +49,45 @@ def timed(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--wrapper", type=int, default=0, choices=(0, 1, 2), help="0 raw, 1 zlib, 2 gzip")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = da.Context(0)
     L = da.load()
-    res = {"metric": "batched encode, device-resident (best of %d)" % a.reps, "workloads": {}}
+    w = a.wrapper
+    hdr = da.BLANK_GZIP_HEADER
+    res = {"metric": "batched encode, device-resident (best of %d)" % a.reps, "wrapper": w, "workloads": {}}
     for name, datas in workloads().items():
         nbytes = sum(map(len, datas))
         ins = [torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda() for d in datas]
         cat = torch.cat(ins)
-        outs = [torch.empty(L.mi355_deflate_bound_ex(len(d), 0, 0, 0), dtype=torch.uint8, device="cuda") for d in datas]
-        cat_out = torch.empty(L.mi355_deflate_bound_ex(nbytes, 0, 0, 0) + 64, dtype=torch.uint8, device="cuda")
+        outs = [torch.empty(L.mi355_deflate_bound_ex(len(d), w, len(hdr), 0), dtype=torch.uint8, device="cuda") for d in datas]
+        cat_out = torch.empty(L.mi355_deflate_bound_ex(nbytes, w, len(hdr), 0) + 64, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         row = {"items": len(datas), "bytes": nbytes}
         for lvl, opt in (("default", da.Compression.Default), ("fast", da.Compression.Fast)):
+            o_c = da.CompressionOptions.from_(opt).to_c(2, 0, 0)
+            n_out = C.c_size_t(0)
+
             def loop():
                 for x, o in zip(ins, outs):
-                    ctx.encode_device(x.data_ptr(), x.numel(), o.data_ptr(), o.numel(), opt)
+                    if w == 2:
+                        rc = L.mi355_deflate_encode_device_gzip(ctx._h, C.c_void_p(x.data_ptr()), x.numel(), C.byref(o_c), hdr, len(hdr),
+                                                                C.c_void_p(o.data_ptr()), o.numel(), C.byref(n_out), None)
+                        assert rc == 0, rc
+                    else:
+                        ctx.encode_device(x.data_ptr(), x.numel(), o.data_ptr(), o.numel(), opt, wrapper=w)
 
             def one_batch():
-                ctx.encode_batch_device(ins, outs, options=opt)
+                if w == 2:
+                    ctx.encode_batch_device_gzip(ins, outs, options=opt)
+                else:
+                    ctx.encode_batch_device(ins, outs, options=opt, wrapper=w)
 
             def concat():
-                ctx.encode_device(cat.data_ptr(), cat.numel(), cat_out.data_ptr(), cat_out.numel(), opt)
+                ctx.encode_device(cat.data_ptr(), cat.numel(), cat_out.data_ptr(), cat_out.numel(), opt, wrapper=w)
             t_loop, t_batch, t_cat = timed(loop, a.reps), timed(one_batch, a.reps), timed(concat, a.reps)
-            ctx.encode_batch_device(ins, outs, options=opt)
+            one_batch()
             bi = ctx.batch_info()
             row[lvl] = {
                 "loop_ms": round(t_loop, 3), "loop_gbps": round(nbytes / t_loop / 1e6, 3),
