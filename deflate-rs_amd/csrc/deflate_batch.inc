@@ -6,7 +6,9 @@
 // by a search over the stage's running sums (stages.h batch_item_of).  The stages that are one workgroup per call (k_small_fix,
 // k_plan, the zlib tail, the gzip tail) are one workgroup per item.  A gzip batch (mi355_deflate_encode_batch[_device]_gzip) adds
 // kb_crc, the CRC-32 of every item in one flat grid, and kb_gzip_tail, which writes the item's header and trailer with byte stores
-// after the pack (a header has any length, so an item's stream starts on any byte of a word).  DESIGN.md section 10.
+// after the pack (a header has any length, so an item's stream starts on any byte of a word).  At the levels without a hash (RLE,
+// Huffman only) kb_nohash stands where kb_sort and kb_walk stand: k_rle over the items' tiles, or the items' M slices cleared.
+// DESIGN.md section 10.
 namespace mi355 {
 
 struct BatchItem {
@@ -26,7 +28,7 @@ struct BatchItem {
     uint8_t* out;
 };
 // the stages with a grid of their own per item (a row of running sums each)
-enum : uint32_t { BS_SORT, BS_WALK, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_CRC, BS_N };
+enum : uint32_t { BS_SORT, BS_WALK, BS_RLE, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_CRC, BS_N };
 struct BatchArgs {
     const BatchItem* it;
     const uint32_t* pre;  // BS_N rows of n_items + 1 running sums of workgroups
@@ -71,6 +73,29 @@ __global__ __launch_bounds__(M3T) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     else
         m3_epoch<HAS_Q, false, SINGLE>(s_T, s_next, e, part, it.in, it.n, it.S, it.B, it.M, Mq, checks, checks_q, aligned16, sg,
                                        batch_no_override(), split, ms, mqs, &it.st->sort_bad);
+}
+
+// The match stage of a set at a level without a hash, one workgroup per tile of RT positions (the grid run_encode gives k_rle).
+// RLE: k_rle of the item -- its run table into M, its restart steps into adv; a run ends with the item (k_rle bounds every read and
+// every run by n), wherever the item lies and whatever follows it.  Huffman only: the item's M slice cleared (n + 64 entries, the
+// fill of run_encode), as whole 16-byte lines: M is 256-byte aligned and its slice is padded to the next 256 bytes (carve).
+// Workgroup 0 of an item does what kb_sort does on the side: the item's scalars cleared, its one segment end set.  Nothing in this
+// kernel reads either (one segment end: k_rle does not look at it).
+template <bool RLE>
+__global__ __launch_bounds__(256) void kb_nohash(BatchArgs bat_) {
+    uint32_t local, count;
+    const BatchItem& it = bat_.it[batch_locate(bat_, BS_RLE, local, count)];
+    if (local == 0) {
+        uint32_t* const sc = reinterpret_cast<uint32_t*>(it.st);
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(DevScalars) / 4); i += 256) sc[i] = 0;
+        if (threadIdx.x == 0) *it.seg_ends = it.n;
+    }
+    if (RLE) {
+        k_rle_body(local, it.in, it.n, it.M, it.adv, SegEnds{it.seg_ends, 1u});
+    } else {
+        const uint32_t lo = local * RT, hi = local + 1 == count ? ((it.n + 64 + 3) & ~3u) : lo + RT;
+        for (uint32_t i = lo + threadIdx.x * 4; i < hi; i += 256 * 4) *reinterpret_cast<uint4*>(it.M + i) = make_uint4(0, 0, 0, 0);
+    }
 }
 
 __global__ __launch_bounds__(256) void kb_adv(BatchArgs bat_, ParseCfg cfg) {
@@ -172,7 +197,7 @@ __global__ __launch_bounds__(64) void kb_zlib_tail(BatchArgs bat_) {
 
 // k_crc_part and k_crc_fold of an item in one kernel: a thread runs the table CRC over its CRC_CHUNK bytes (the body of k_crc_part),
 // multiplies it by x^(8 * bytes of the item behind the chunk) and the products are XOR-ed: over the wave by shuffles, over the
-// workgroup through LDS, then one atomicXor into the item's scalar (cleared by the item's kb_sort).  No per-chunk words in memory.
+// workgroup through LDS, then one atomicXor into the item's scalar (cleared by the item's kb_sort / kb_nohash).  No per-chunk words in memory.
 __global__ __launch_bounds__(256) void kb_crc(BatchArgs bat_) {
     __shared__ uint32_t s_wave[4];
     uint32_t local, count;
@@ -237,8 +262,10 @@ struct BatchHeaders {
 };
 
 // Can the batched kernels take this item?  (Else: the one-input path, after the launch sets.)
+// (Every level but Lazy with a quarter budget of 0 checks; the levels without a hash -- RLE, Huffman only -- have kb_nohash.)
 bool batch_takes(const ParseCfg& cfg, uint64_t n) {
-    return MI355_SMALL_TAIL && cfg_hashing(cfg) && !(cfg.use_quarter && cfg_cq(cfg) == 0) && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
+    const bool level = !cfg_hashing(cfg) || !(cfg.use_quarter && cfg_cq(cfg) == 0);
+    return MI355_SMALL_TAIL && level && n > 0 && (n + SEG - 1) / SEG <= SMALL_TAIL_SEGS;
 }
 
 enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
@@ -247,6 +274,7 @@ enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
 int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const mi355_deflate_opts* o, const ParseCfg& cfg,
                      hipStream_t st, const BatchHeaders& gz, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
     const bool zlib = o->wrapper == 1, gzip = o->wrapper == 2;
+    const bool hashing = cfg_hashing(cfg);  // (else: no sort, no walk, no Q1 -- kb_nohash is the match stage)
     const uint32_t cq = cfg_cq(cfg);
     const bool has_q = cfg_has_q(cfg);
     // the items' workspaces, one behind the other in the context's one workspace
@@ -288,7 +316,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     uint64_t epochs = 0;
     for (uint32_t i = 0; i < k; i++) epochs += (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
     const uint32_t cus = c->n_cu ? c->n_cu : 256u;
-    const WalkPlan plan = walk_plan(epochs, c->n_cu);
+    const WalkPlan plan = hashing ? walk_plan(epochs, c->n_cu) : WalkPlan{};
     const bool single = plan.single;
     const uint32_t split = single ? plan.split * 2 : plan.split;
     for (uint32_t s = 0; s < BS_N; s++) hpre[(size_t)s * (k + 1)] = 0;
@@ -300,7 +328,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         d.n = (uint32_t)v[i].n;
         d.K0 = w.K0;
         d.nb_max = w.nb_max;
-        d.q1_check = v[i].n >= MAX_BUFFER_LENGTH ? 1u : 0u;
+        d.q1_check = (hashing && v[i].n >= MAX_BUFFER_LENGTH) ? 1u : 0u;
         d.out_words = (uint32_t)(v[i].need / 4);
         d.bit_base = zlib ? 16u : 0u;
         if (gzip) {
@@ -336,8 +364,9 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         d.st = dst + i;
         d.out = v[i].d_out;
         const uint64_t n_ep = (v[i].n + WINDOW_SIZE - 1) / WINDOW_SIZE;
-        const uint64_t wg[BS_N] = {n_ep, n_ep * split, cdiv(v[i].n, ADV_TILE), cdiv(w.K0, 4), cdiv(w.K0, 4), (uint64_t)w.nb_max * PSPLIT,
-                                   w.nb_max, (uint64_t)w.nb_max * PSPLIT, cdiv(v[i].n, ADLER_CHUNK), gzip ? cdiv(v[i].n, 256 * CRC_CHUNK) : 0u};
+        const uint64_t wg[BS_N] = {hashing ? n_ep : 0u, hashing ? n_ep * split : 0u, hashing ? 0u : cdiv(v[i].n, RT), cdiv(v[i].n, ADV_TILE),
+                                   cdiv(w.K0, 4), cdiv(w.K0, 4), (uint64_t)w.nb_max * PSPLIT, w.nb_max, (uint64_t)w.nb_max * PSPLIT,
+                                   cdiv(v[i].n, ADLER_CHUNK), gzip ? cdiv(v[i].n, 256 * CRC_CHUNK) : 0u};
         for (uint32_t s = 0; s < BS_N; s++) {
             const uint64_t t = (uint64_t)hpre[(size_t)s * (k + 1) + i] + wg[s];
             if (t > 0x7fffffffull) return MI355_E_ARG;  // (a launch set of at most 256 MiB of input is far below this)
@@ -347,25 +376,33 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     auto total = [&](uint32_t s) { return hpre[(size_t)s * (k + 1) + k]; };
     const BatchArgs a{reinterpret_cast<const BatchItem*>(c->b_dev), reinterpret_cast<const uint32_t*>(c->b_dev + sizeof(BatchItem) * k), k};
     HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, gz_at + gz_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dst, 0, state_bytes, st));  // (the flags behind the scalars: k_sort clears the scalars themselves)
-    // ---- match table ----
-    if (c->sort_mode == 1)
-        hipLaunchKernelGGL(kb_sort<1>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, c->sort_break ? 3u : 1u);
-    else
-        hipLaunchKernelGGL(kb_sort<0>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, 1u);
+    HIPCHK(c, hipMemsetAsync(dst, 0, state_bytes, st));  // (the flags behind the scalars: kb_sort / kb_nohash clear the scalars themselves)
+    // ---- match table (the levels without a hash: kb_nohash, and neither sort nor walk) ----
 #define MI355_BWALK(Q, SNG) hipLaunchKernelGGL((kb_walk<Q, SNG>), dim3(total(BS_WALK)), dim3(M3T), 0, st, a, cfg.checks, Q ? cq : 0u, split)
-    if (has_q && single)
-        MI355_BWALK(true, true);
-    else if (has_q)
-        MI355_BWALK(true, false);
-    else if (single)
-        MI355_BWALK(false, true);
-    else
-        MI355_BWALK(false, false);
+    if (!hashing) {
+        if (cfg.mode == MODE_RLE)
+            hipLaunchKernelGGL(kb_nohash<true>, dim3(total(BS_RLE)), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL(kb_nohash<false>, dim3(total(BS_RLE)), dim3(256), 0, st, a);
+    } else {
+        if (c->sort_mode == 1)
+            hipLaunchKernelGGL(kb_sort<1>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, c->sort_break ? 3u : 1u);
+        else
+            hipLaunchKernelGGL(kb_sort<0>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, 1u);
+        if (has_q && single)
+            MI355_BWALK(true, true);
+        else if (has_q)
+            MI355_BWALK(true, false);
+        else if (single)
+            MI355_BWALK(false, true);
+        else
+            MI355_BWALK(false, false);
+    }
 #undef MI355_BWALK
     // ---- parse: speculative segment entries, the check and repair, the block table (k_small_fix), compaction ----
+    // (RLE: k_rle has written the steps of that level, as in run_encode)
     const bool in_emit = steps_in_emit(c, cfg, 1);
-    if (!in_emit) hipLaunchKernelGGL(kb_adv, dim3(total(BS_ADV)), dim3(256), 0, st, a, cfg);
+    if (!in_emit && cfg.mode != MODE_RLE) hipLaunchKernelGGL(kb_adv, dim3(total(BS_ADV)), dim3(256), 0, st, a, cfg);
     if (in_emit) {
         hipLaunchKernelGGL(kb_emit<true>, dim3(total(BS_EMIT)), dim3(256), 0, st, a, cfg);
         hipLaunchKernelGGL(kb_small_fix<true>, dim3(k), dim3(SMALL_FIX_T), 0, st, a, cfg);
@@ -396,8 +433,8 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(hst, dst, state_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    bool sort_bad = false;
-    for (uint32_t i = 0; i < k; i++) sort_bad |= hst[i].sort_bad != 0;
+    bool sort_bad = false;  // (only the walk sets it)
+    for (uint32_t i = 0; i < k && hashing; i++) sort_bad |= hst[i].sort_bad != 0;
     if (sort_bad) {  // (never seen on MI355X; the set is done again with ballot ranks, as run_encode does)
         if (c->sort_mode == 0) {
             c->err = "batched walk: a bucket out of order with ballot ranks";

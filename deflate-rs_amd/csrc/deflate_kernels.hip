@@ -1634,14 +1634,15 @@ constexpr uint32_t RLE_UNITS = RT / 16 + 17;        // 16-position units with bi
 constexpr uint32_t RLE_BYTES = 16 + RLE_UNITS * 16; // staged bytes: s[j] = in[E - 16 + j]
 // (adv: the restart step of the RLE level -- rle.rs:46-69: a run of three or more is taken whole, else one literal -- needs
 // nothing but the run at the position, so it is written here and k_adv is not launched for this level.)
-__global__ __launch_bounds__(256) void k_rle(const uint8_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ R,
-                                             uint16_t* __restrict__ adv, SegEnds sg) {
+// (bx_: the tile -- the workgroup of a call's own launch, or of an item in a batch's flat grid, deflate_batch.inc kb_nohash)
+__device__ __forceinline__ void k_rle_body(uint32_t bx_, const uint8_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ R,
+                                           uint16_t* __restrict__ adv, SegEnds sg) {
     __shared__ __attribute__((aligned(16))) uint8_t s[RLE_BYTES];
     __shared__ uint32_t eb[RLE_UNITS + 1];
     __shared__ __attribute__((aligned(16))) uint32_t so[RT];
     __shared__ __attribute__((aligned(16))) uint16_t sa[RT];
     const uint32_t tid = threadIdx.x;
-    const uint64_t E = (uint64_t)blockIdx.x * RT;
+    const uint64_t E = (uint64_t)bx_ * RT;
     const bool al = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     for (uint32_t k = tid; k < RLE_BYTES / 16; k += 256) {
         const int64_t g0 = (int64_t)E - 16 + 16 * (int64_t)k;
@@ -1740,6 +1741,10 @@ __global__ __launch_bounds__(256) void k_rle(const uint8_t* __restrict__ in, uin
             for (uint32_t j = 0; j < 4 && g + j < n; j++) R[g + j] = so[i + j];
         }
     }
+}
+__global__ __launch_bounds__(256) void k_rle(const uint8_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ R,
+                                             uint16_t* __restrict__ adv, SegEnds sg) {
+    k_rle_body(blockIdx.x, in, n, R, adv, sg);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -245,9 +245,10 @@ int mi355_deflate_last_blocks(mi355_deflate_ctx* ctx, mi355_block_info* out, siz
  * Item i's output is byte for byte what mi355_deflate_encode gives for that item alone with the same opts (whatever the
  * other items, their order or their number).  One opts for the whole batch: every level, wrapper 0 (raw) or 1 (zlib),
  * MI355_FLUSH_FINISH; wrapper 2 or a sync flush is MI355_E_ARG, lazy_if_less_than < 3 with Lazy MI355_E_UNSUPPORTED.
- * Items of up to 2 MiB at the levels with a hash table are encoded together by the batched kernels; longer items, the
- * levels without a hash (RLE, Huffman-only), empty items and the items whose first block fires the hash re-warm (A.4 Q1)
- * or whose speculative parse fails go through the one-input path after them.
+ * Items of up to 2 MiB are encoded together by the batched kernels, at the levels with a hash table and at those without
+ * one (RLE, Huffman-only); longer items, empty items and the items whose first block fires the hash re-warm (A.4 Q1; the
+ * levels with a hash only) or whose speculative parse fails (at RLE: runs too long to re-join, zero fill first of all) go
+ * through the one-input path after them.
  * An item with out_cap < mi355_deflate_bound_ex(in_len, opts->wrapper, 0, 0) gets MI355_E_OUT_TOO_SMALL and the size needed in
  * out_len; an item may get MI355_E_REF_PANIC under MI355_COMPAT_Q13.  Neither disturbs the other items.  The call returns
  * MI355_OK when every item is OK, else the status of the first failing item; errors of the call itself (NULL items with

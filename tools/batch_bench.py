@@ -1,15 +1,18 @@
 """tools/batch_bench.py -- the batched encode against a loop of one-input calls and against one call on the concatenation.
 
-Device-resident inputs, Default and Fast.  For each workload: (a) a loop of mi355_deflate_encode_device over the items, (b) one
+Device-resident inputs; --levels picks the levels (default: Default and Fast; also rle, huffman_only, best).  For each workload: (a) a loop of mi355_deflate_encode_device over the items, (b) one
 mi355_deflate_encode_batch_device call, (c) one mi355_deflate_encode_device call on the concatenation of the same bytes (other
 output bytes: the throughput ceiling, a yardstick only).  Every shape is warmed up before its timed window; every timed call
 ends in a synchronise.  --wrapper 1 / 2 times the same workloads with zlib / gzip framing (2: the blank header, the loop over
 mi355_deflate_encode_device_gzip, the batch through mi355_deflate_encode_batch_device_gzip; profiles/batch_bench_gzip.json holds
-a run of 2 and of 1 from one session).  Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--wrapper W] [--out FILE]"""
+a run of 2 and of 1 from one session).  --workloads picks the workloads: by default the four of generated text, and with a level
+without a hash (rle, huffman_only) also 256x64KiB_runs, rows of runs of equal bytes (the generated text has no run longer than 5).
+Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--wrapper W] [--levels L,L] [--workloads W,W] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
 import os
+import random
 import sys
 import time
 
@@ -23,14 +26,38 @@ import datagen  # noqa: E402
 import deflate_amd as da  # noqa: E402
 
 
-def workloads():
+LEVELS = {"default": da.Compression.Default, "fast": da.Compression.Fast, "best": da.Compression.Best,
+          "rle": da.CompressionOptions.rle(), "huffman_only": da.CompressionOptions.huffman_only()}
+TEXT_WORKLOADS = ("256x64KiB", "1024x4KiB", "64x1MiB", "100xpg11")
+RUNS_WORKLOAD = "256x64KiB_runs"
+
+
+def run_rows(n, seed, width=1024):
+    """n bytes of image-like rows of `width` bytes: every row is runs of equal bytes, their lengths drawn from 1..200 (the last one
+    of a row cut at its end); a run's byte is never its neighbour's, so a run is as long as it was drawn.  Seeded."""
+    rnd = random.Random(seed)
+    out = bytearray()
+    v = rnd.randrange(256)
+    while len(out) < n:
+        left = width
+        while left:
+            r = min(rnd.randint(1, 200), left)
+            v = (v + rnd.randint(1, 255)) & 255
+            out += bytes([v]) * r
+            left -= r
+    return bytes(out[:n])
+
+
+def workloads(names):
     pg = open(os.path.join(ROOT, "tests", "golden", "ref_inputs", "pg11.txt"), "rb").read()
-    return {
-        "256x64KiB": [datagen.text_like(64 << 10, 1000 + k) for k in range(256)],
-        "1024x4KiB": [datagen.text_like(4 << 10, 5000 + k) for k in range(1024)],
-        "64x1MiB": [datagen.text_like(1 << 20, 9000 + k) for k in range(64)],
-        "100xpg11": [pg] * 100,
+    make = {
+        "256x64KiB": lambda: [datagen.text_like(64 << 10, 1000 + k) for k in range(256)],
+        "1024x4KiB": lambda: [datagen.text_like(4 << 10, 5000 + k) for k in range(1024)],
+        "64x1MiB": lambda: [datagen.text_like(1 << 20, 9000 + k) for k in range(64)],
+        "100xpg11": lambda: [pg] * 100,
+        RUNS_WORKLOAD: lambda: [run_rows(64 << 10, 13000 + k) for k in range(256)],
     }
+    return {name: make[name]() for name in names}
 
 
 def timed(fn, reps):
@@ -50,14 +77,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--wrapper", type=int, default=0, choices=(0, 1, 2), help="0 raw, 1 zlib, 2 gzip")
+    ap.add_argument("--levels", default="default,fast", help="comma-separated: " + ", ".join(LEVELS))
+    ap.add_argument("--workloads", default=None, help="comma-separated: %s, %s (default: the text ones, and the runs with a level "
+                    "without a hash)" % (", ".join(TEXT_WORKLOADS), RUNS_WORKLOAD))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    levels = [x for x in a.levels.split(",") if x]
+    for x in levels:
+        if x not in LEVELS:
+            ap.error("--levels: %r is none of %s" % (x, ", ".join(LEVELS)))
+    if a.workloads:
+        names = [x for x in a.workloads.split(",") if x]
+        for x in names:
+            if x not in TEXT_WORKLOADS + (RUNS_WORKLOAD,):
+                ap.error("--workloads: %r is none of %s" % (x, ", ".join(TEXT_WORKLOADS + (RUNS_WORKLOAD,))))
+    else:
+        names = list(TEXT_WORKLOADS) + ([RUNS_WORKLOAD] if any(x in ("rle", "huffman_only") for x in levels) else [])
     ctx = da.Context(0)
     L = da.load()
     w = a.wrapper
     hdr = da.BLANK_GZIP_HEADER
     res = {"metric": "batched encode, device-resident (best of %d)" % a.reps, "wrapper": w, "workloads": {}}
-    for name, datas in workloads().items():
+    for name, datas in workloads(names).items():
         nbytes = sum(map(len, datas))
         ins = [torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda() for d in datas]
         cat = torch.cat(ins)
@@ -65,7 +106,7 @@ def main():
         cat_out = torch.empty(L.mi355_deflate_bound_ex(nbytes, w, len(hdr), 0) + 64, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         row = {"items": len(datas), "bytes": nbytes}
-        for lvl, opt in (("default", da.Compression.Default), ("fast", da.Compression.Fast)):
+        for lvl, opt in ((x, LEVELS[x]) for x in levels):
             o_c = da.CompressionOptions.from_(opt).to_c(2, 0, 0)
             n_out = C.c_size_t(0)
 
@@ -96,6 +137,8 @@ def main():
                 "batch_over_loop": round(t_loop / t_batch, 2), "batch_over_concat": round(t_cat / t_batch, 3),
                 "n_batched": bi["n_batched"], "n_single": bi["n_single"], "sub_batches": bi["sub_batches"],
             }
+            if bi["n_spec_single"]:  # (items whose speculative parse failed in the set and that were encoded again singly)
+                row[lvl]["n_spec_single"] = bi["n_spec_single"]
         res["workloads"][name] = row
     ctx.close()
     line = json.dumps(res)
