@@ -8,6 +8,8 @@
 // kb_crc, the CRC-32 of every item in one flat grid, and kb_gzip_tail, which writes the item's header and trailer with byte stores
 // after the pack (a header has any length, so an item's stream starts on any byte of a word).  At the levels without a hash (RLE,
 // Huffman only) kb_nohash stands where kb_sort and kb_walk stand: k_rle over the items' tiles, or the items' M slices cleared.
+// A packed batch (mi355_deflate_encode_batch_packed[_device]) adds kb_place between kb_plan and kb_pack: the items' exact lengths
+// are known there, and a scan over them gives every item its place in the caller's one arena (BatchItem::out, written on the device).
 // DESIGN.md section 10.
 namespace mi355 {
 
@@ -25,7 +27,7 @@ struct BatchItem {
     BlockHeader* hdr;
     BlockPlan* plan;
     DevState* st;  // the item's scalars and flags
-    uint8_t* out;
+    uint8_t* out;  // a packed set: written by kb_place; nullptr = not placed (kb_pack, kb_zlib_tail_placed and kb_gzip_tail return at once)
 };
 // the stages with a grid of their own per item (a row of running sums each)
 enum : uint32_t { BS_SORT, BS_WALK, BS_RLE, BS_ADV, BS_EMIT, BS_COMPACT, BS_HIST, BS_HEADER, BS_PACK, BS_ADLER, BS_CRC, BS_N };
@@ -163,6 +165,7 @@ template <uint32_t PKT>
 __global__ __launch_bounds__(PKT) void kb_pack(BatchArgs bat_, uint32_t compat) {
     uint32_t local, count;
     const BatchItem& it = bat_.it[batch_locate(bat_, BS_PACK, local, count)];
+    if (!it.out) return;  // (a packed set: the item takes no bytes -- kb_place)
     const uint8_t* in = it.in;
     uint32_t n = it.n, piece = 0;
     const uint32_t* dtok = it.dtok;
@@ -191,6 +194,14 @@ __global__ __launch_bounds__(256) void kb_adler_part(BatchArgs bat_) {
 // k_adler_fold and k_zlib_frame of an item, one after the other in one lane
 __global__ __launch_bounds__(64) void kb_zlib_tail(BatchArgs bat_) {
     const BatchItem& it = bat_.it[blockIdx.x];
+    k_adler_fold_body(0u, it.n, &it.st->sc);
+    k_zlib_frame_body(0u, &it.st->sc, it.out, 1u);
+}
+// ... of a packed set: nothing for an item that kb_place did not place.  (A kernel of its own: with the test inside it,
+// kb_zlib_tail came out with one scalar register less, and the kernels of the plain batch stay as they are.)
+__global__ __launch_bounds__(64) void kb_zlib_tail_placed(BatchArgs bat_) {
+    const BatchItem& it = bat_.it[blockIdx.x];
+    if (!it.out) return;
     k_adler_fold_body(0u, it.n, &it.st->sc);
     k_zlib_frame_body(0u, &it.st->sc, it.out, 1u);
 }
@@ -225,6 +236,7 @@ __global__ __launch_bounds__(256) void kb_crc(BatchArgs bat_) {
 // k_gzip_frame of an item: its header from the set's header bytes, CRC-32 and length behind the stream
 __global__ __launch_bounds__(64) void kb_gzip_tail(BatchArgs bat_, const uint8_t* __restrict__ gz) {
     const BatchItem& it = bat_.it[blockIdx.x];
+    if (!it.out) return;
     DevScalars* sc = &it.st->sc;
     uint8_t* out = it.out;
     const uint8_t* hdr = gz + it.gz_off;
@@ -232,6 +244,85 @@ __global__ __launch_bounds__(64) void kb_gzip_tail(BatchArgs bat_, const uint8_t
 #define BX_ 0u
 #include "body_k_gzip_frame.inc"
 #undef BX_
+}
+
+// The placement of a packed set, one workgroup of PLACE_T threads behind kb_plan: an item's stream takes len = stream_bytes(its
+// total_bits) bytes -- none where its speculative parse failed or Q1 fired (the one-input path encodes it after the sets) or where
+// the reference panics -- and owns align_up(len, align) bytes of the arena.  A 64-bit exclusive scan of those, PLACE_T items a
+// round (shuffles inside a wave, the waves' sums through LDS, the running end carried from round to round), started at the end the
+// launch sets before this one left, gives every item its offset as if the arena had no end.  An item whose region ends at or
+// below `cap` gets its pointer; one that would cross it -- and one without bytes -- gets nullptr and is left alone by kb_pack and
+// the tails.  The item's table entry goes to the caller's table (if there is one), the set's end to *tail_out, behind the items'
+// DevStates, where the set's one copy back picks it up.
+constexpr uint32_t PLACE_T = 1024;
+struct PlaceArgs {
+    uint8_t* base;        // the address of arena offset tail0
+    uint64_t tail0, cap;  // where the set starts; the arena's capacity
+    uint32_t align, wrapper;
+    const uint32_t* idx;        // the items' places in the caller's array (the table's order)
+    mi355_packed_entry* table;  // or nullptr
+    uint64_t* tail_out;
+};
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int off) {
+    const uint32_t lo = __shfl_up((uint32_t)v, off, 64), hi = __shfl_up((uint32_t)(v >> 32), off, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+__global__ __launch_bounds__(PLACE_T) void kb_place(BatchArgs bat_, PlaceArgs p) {
+    __shared__ uint64_t s_wave[PLACE_T / 64];
+    BatchItem* const items = const_cast<BatchItem*>(bat_.it);  // (the descriptors are the context's device memory)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t amask = (uint64_t)p.align - 1;
+    uint64_t end = p.tail0;
+    for (uint32_t i0 = 0; i0 < bat_.n_items; i0 += PLACE_T) {
+        const uint32_t i = i0 + tid;
+        uint64_t len = 0;
+        int32_t status = MI355_OK;
+        if (i < bat_.n_items) {
+            const DevScalars* sc = &items[i].st->sc;
+            if (spec_failed(sc))
+                len = 0;
+            else if (sc->ref_panic)
+                status = MI355_E_REF_PANIC;
+            else
+                len = stream_bytes(sc->total_bits, p.wrapper, items[i].gz_len, false);
+        }
+        const uint64_t need = (len + amask) & ~amask;
+        uint64_t incl = need;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint64_t y = shfl_up_u64(incl, off);
+            if (lane >= (uint32_t)off) incl += y;
+        }
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        uint64_t wbase = 0, total = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < PLACE_T / 64; k++) {
+            const uint64_t y = s_wave[k];
+            if (k < wv) wbase += y;
+            total += y;
+        }
+        const uint64_t off = end + wbase + (incl - need);
+        if (i < bat_.n_items) {
+            const bool fits = off + need <= p.cap;
+            if (len && !fits) status = MI355_E_OUT_TOO_SMALL;
+            items[i].out = (len && fits) ? p.base + (off - p.tail0) : nullptr;
+            if (p.table) p.table[p.idx[i]] = mi355_packed_entry{off, len, status, 0u};
+        }
+        end += total;
+        __syncthreads();  // (the next round's sums behind this round's reads of them)
+    }
+    if (tid == 0) *p.tail_out = end;
+}
+
+// The clear of a packed set's range (kb_pack ORs its bits in), behind kb_place and sized from its scan: the words from the set's
+// start to its end, or to the arena's if that comes first (regions are whole words, so every region that fits ends at or before
+// the last whole word below cap).  The pad bytes of the regions are zero because of it.  (One runtime fill in front of the set
+// over all the set could reach -- the sum of the items' bounds -- measured the same or worse: DESIGN.md section 10.)
+__global__ __launch_bounds__(256) void kb_clear(uint32_t* __restrict__ base, uint64_t tail0, uint64_t cap, const uint64_t* __restrict__ end) {
+    const uint64_t stop = *end < cap ? *end : cap;
+    const uint64_t words = stop > tail0 ? (stop - tail0) / 4 : 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (uint64_t)gridDim.x * 256) base[i] = 0;
 }
 
 }  // namespace mi355
@@ -270,9 +361,24 @@ bool batch_takes(const ParseCfg& cfg, uint64_t n) {
 
 enum BatchOutcome { BO_OK, BO_Q1, BO_SPEC, BO_PANIC };
 
+// The arena of a packed batch (mi355_deflate_encode_batch_packed[_device]) as the launch sets see it.
+struct PackedOut {
+    uint8_t* d_arena;  // the caller's device arena (_device), or nullptr: every set goes through the context's staging (host)
+    uint8_t* h_arena;  // the caller's host arena, or nullptr
+    uint64_t cap;
+    uint32_t align;
+    mi355_packed_entry* d_table;  // or nullptr
+    uint64_t tail;                // the end of the regions so far, as if the arena had no end
+    // of the set under way: the device address of offset `tail`, and the items' offsets (written by batch_launch_set)
+    uint8_t* set_base;
+    std::vector<uint64_t> off;
+    uint64_t up(uint64_t len) const { return (len + align - 1) & ~(uint64_t)(align - 1); }
+};
+
 // One launch set over v[0..k): the kernels, one copy of the items' scalars back, one wait.  out_len / outcome per item.
 int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const mi355_deflate_opts* o, const ParseCfg& cfg,
-                     hipStream_t st, const BatchHeaders& gz, size_t* out_len, BatchOutcome* outcome, DevScalars* sums) {
+                     hipStream_t st, const BatchHeaders& gz, size_t* out_len, BatchOutcome* outcome, DevScalars* sums,
+                     PackedOut* pk = nullptr) {
     const bool zlib = o->wrapper == 1, gzip = o->wrapper == 2;
     const bool hashing = cfg_hashing(cfg);  // (else: no sort, no walk, no Q1 -- kb_nohash is the match stage)
     const uint32_t cq = cfg_cq(cfg);
@@ -296,8 +402,12 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             gz_bytes += h.hdr_len;
         }
     }
-    const size_t desc_bytes = align_up(gz_at + gz_bytes, 256);
-    const size_t state_bytes = sizeof(DevState) * k;
+    // a packed set: the items' places in the caller's array behind the header bytes (kb_place writes the table in that order), and
+    // one more DevState's room behind the items' for the set's end
+    const size_t idx_at = align_up(gz_at + gz_bytes, 4);
+    const size_t up_bytes = pk ? idx_at + sizeof(uint32_t) * k : gz_at + gz_bytes;
+    const size_t desc_bytes = align_up(up_bytes, 256);
+    const size_t state_bytes = sizeof(DevState) * (pk ? k + 1 : k);
     rc = ensure_buf(c, &c->b_dev, &c->b_dev_cap, desc_bytes + state_bytes);
     if (rc) return rc;
     if (desc_bytes + state_bytes > c->b_host_cap) {
@@ -329,7 +439,8 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         d.K0 = w.K0;
         d.nb_max = w.nb_max;
         d.q1_check = (hashing && v[i].n >= MAX_BUFFER_LENGTH) ? 1u : 0u;
-        d.out_words = (uint32_t)(v[i].need / 4);
+        d.out_words = pk ? 0u : (uint32_t)(v[i].need / 4);  // (a packed set's range is cleared as a whole: kb_clear)
+        if (pk) reinterpret_cast<uint32_t*>(c->b_host + idx_at)[i] = (uint32_t)v[i].idx;
         d.bit_base = zlib ? 16u : 0u;
         if (gzip) {
             const mi355_gzip_header h = gz.of(v[i].idx);
@@ -375,8 +486,14 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
     }
     auto total = [&](uint32_t s) { return hpre[(size_t)s * (k + 1) + k]; };
     const BatchArgs a{reinterpret_cast<const BatchItem*>(c->b_dev), reinterpret_cast<const uint32_t*>(c->b_dev + sizeof(BatchItem) * k), k};
-    HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, gz_at + gz_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->b_dev, c->b_host, up_bytes, hipMemcpyHostToDevice, st));
+    uint64_t pk_reach = 0;
     HIPCHK(c, hipMemsetAsync(dst, 0, state_bytes, st));  // (the flags behind the scalars: kb_sort / kb_nohash clear the scalars themselves)
+    if (pk) {  // as far as the set can reach and the arena goes: the grid of kb_clear
+        uint64_t reach = 0;
+        for (uint32_t i = 0; i < k; i++) reach += pk->up(v[i].need);
+        pk_reach = std::min(reach, pk->cap > pk->tail ? pk->cap - pk->tail : 0);
+    }
     // ---- match table (the levels without a hash: kb_nohash, and neither sort nor walk) ----
 #define MI355_BWALK(Q, SNG) hipLaunchKernelGGL((kb_walk<Q, SNG>), dim3(total(BS_WALK)), dim3(M3T), 0, st, a, cfg.checks, Q ? cq : 0u, split)
     if (!hashing) {
@@ -418,13 +535,23 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
         hipLaunchKernelGGL(kb_block_hist<256>, dim3(total(BS_HIST)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(kb_block_header, dim3(total(BS_HEADER)), dim3(128), 0, st, a);
     hipLaunchKernelGGL(kb_plan, dim3(k), dim3(1024), 0, st, a, (uint32_t)o->compat);
+    if (pk)
+        hipLaunchKernelGGL(kb_place, dim3(1), dim3(PLACE_T), 0, st, a,
+                           PlaceArgs{pk->set_base, pk->tail, pk->cap, pk->align, (uint32_t)o->wrapper,
+                                     reinterpret_cast<const uint32_t*>(c->b_dev + idx_at), pk->d_table, reinterpret_cast<uint64_t*>(dst + k)});
+    if (pk && pk_reach)
+        hipLaunchKernelGGL(kb_clear, dim3((uint32_t)std::min<uint64_t>(cdiv(pk_reach, 256 * 4 * 8), 2048)), dim3(256), 0, st,
+                           reinterpret_cast<uint32_t*>(pk->set_base), pk->tail, pk->cap, reinterpret_cast<const uint64_t*>(dst + k));
     if (total(BS_PACK) <= cus)
         hipLaunchKernelGGL(kb_pack<PKT_SMALL>, dim3(total(BS_PACK)), dim3(PKT_SMALL), 0, st, a, (uint32_t)o->compat);
     else
         hipLaunchKernelGGL(kb_pack<PKT_LARGE>, dim3(total(BS_PACK)), dim3(PKT_LARGE), 0, st, a, (uint32_t)o->compat);
     if (zlib) {
         hipLaunchKernelGGL(kb_adler_part, dim3(total(BS_ADLER)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(kb_zlib_tail, dim3(k), dim3(64), 0, st, a);
+        if (pk)
+            hipLaunchKernelGGL(kb_zlib_tail_placed, dim3(k), dim3(64), 0, st, a);
+        else
+            hipLaunchKernelGGL(kb_zlib_tail, dim3(k), dim3(64), 0, st, a);
     }
     if (gzip) {
         hipLaunchKernelGGL(kb_crc, dim3(total(BS_CRC)), dim3(256), 0, st, a);
@@ -441,8 +568,10 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             return MI355_E_HIP;
         }
         sort_fell_back(c);
-        return batch_launch_set(c, v, k, o, cfg, st, gz, out_len, outcome, sums);
+        return batch_launch_set(c, v, k, o, cfg, st, gz, out_len, outcome, sums, pk);  // (a packed set places again from the same end)
     }
+    uint64_t end = pk ? pk->tail : 0;
+    if (pk) pk->off.assign(k, 0);
     for (uint32_t i = 0; i < k; i++) {
         const DevScalars& s = hst[i].sc;
         uint64_t wpos = 0;
@@ -463,6 +592,19 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             sums->n_dynamic += s.n_dynamic;
             sums->q13_hits += s.q13_hits;
         }
+        if (pk) {  // the scan of kb_place once more: the items' offsets
+            pk->off[i] = end;
+            end += pk->up(out_len[i]);
+        }
+    }
+    if (pk) {
+        uint64_t dev_end;
+        memcpy(&dev_end, hst + k, sizeof dev_end);
+        if (dev_end != end) {
+            c->err = "packed batch: the device placed the set's items differently from the host's scan of their lengths";
+            return MI355_E_HIP;
+        }
+        pk->tail = end;
     }
     return MI355_OK;
 }
@@ -471,7 +613,7 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
 // host: the items' buffers are the caller's host memory (gathered into the context's device staging per launch set).
 // gz: the items' gzip headers when o->wrapper is 2 (the _gzip entries), else none.
 int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, hipStream_t st, bool host,
-              void* hip_stream, const BatchHeaders& gz) {
+              void* hip_stream, const BatchHeaders& gz, PackedOut* pk = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (c->live_shard) {
         c->err = "this context holds a sharded encode between mi355_shard_begin and mi355_shard_end";
@@ -497,7 +639,8 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
         const size_t need = mi355_deflate_bound_ex(it.in_len, o->wrapper, gz.of(i).hdr_len, 0);
         it.out_len = 0;
         it.status = MI355_OK;
-        if (it.out_cap < need) {
+        if (pk) it.out = nullptr;  // (its address in the arena, once it has one)
+        if (!pk && it.out_cap < need) {
             it.out_len = need;
             it.status = MI355_E_OUT_TOO_SMALL;
         } else if (batch_takes(cfg, it.in_len)) {
@@ -526,28 +669,47 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
             }
             int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, in_off[k]);
             if (rc) return rc;
+            if (pk) {  // the set's part of the arena: as far as the set can reach and the arena goes
+                uint64_t reach = 0;
+                for (uint32_t i = 0; i < k; i++) reach += pk->up(sv[i].need);
+                out_off[k] = (size_t)std::min<uint64_t>(reach, pk->cap > pk->tail ? pk->cap - pk->tail : 0);
+            }
             rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_off[k]);
             if (rc) return rc;
             staged.assign(sv, sv + k);
             for (uint32_t i = 0; i < k; i++) {
                 HIPCHK(c, hipMemcpyAsync(c->d_in + in_off[i], sv[i].d_in, sv[i].n, hipMemcpyHostToDevice, st));
                 staged[i].d_in = c->d_in + in_off[i];
-                staged[i].d_out = c->d_out + out_off[i];
+                staged[i].d_out = pk ? nullptr : c->d_out + out_off[i];
             }
             sv = staged.data();
         }
         out_len.assign(k, 0);
         outcome.assign(k, BO_OK);
-        const int rc = batch_launch_set(c, sv, k, o, cfg, st, gz, out_len.data(), outcome.data(), &sums);
+        const uint64_t tail0 = pk ? pk->tail : 0;
+        if (pk) pk->set_base = host ? c->d_out : pk->d_arena + tail0;  // (beyond the arena's end nothing is placed: never used)
+        const int rc = batch_launch_set(c, sv, k, o, cfg, st, gz, out_len.data(), outcome.data(), &sums, pk);
         if (rc) return rc;
         bi.sub_batches++;
+        uint64_t fit_end = tail0;  // the end of the last region of the set that lies inside the arena
         for (uint32_t i = 0; i < k; i++) {
             mi355_batch_item& it = items[sv[i].idx];
             switch (outcome[i]) {
             case BO_OK:
                 it.out_len = out_len[i];
-                sum_out += out_len[i];
                 bi.n_batched++;
+                if (pk) {
+                    const uint64_t off = pk->off[i], region_end = off + pk->up(out_len[i]);
+                    if (region_end > pk->cap) {  // (kb_place has left it out)
+                        it.status = MI355_E_OUT_TOO_SMALL;
+                        break;
+                    }
+                    it.out = (host ? pk->h_arena : pk->d_arena) + off;
+                    fit_end = region_end;
+                    sum_out += out_len[i];
+                    break;
+                }
+                sum_out += out_len[i];
                 if (host) HIPCHK(c, hipMemcpyAsync(it.out, sv[i].d_out, out_len[i], hipMemcpyDeviceToHost, st));
                 break;
             case BO_PANIC:
@@ -564,17 +726,34 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
                 break;
             }
         }
+        // a packed set's bytes: one copy of its placed range, pad bytes and all
+        if (host && pk && fit_end > tail0) HIPCHK(c, hipMemcpyAsync(pk->h_arena + tail0, c->d_out, fit_end - tail0, hipMemcpyDeviceToHost, st));
         if (host) HIPCHK(c, hipStreamSynchronize(st));
         s0 = s1;
     }
     // ---- the rest, one by one, exactly as the one-input entries do it ----
     std::sort(singles.begin(), singles.end());
     uint32_t q1_any = 0, spec_any = 0;
+    // (a packed batch: into a buffer of the context -- the device staging output, or host memory -- and from there to the arena's
+    // end, once the length is known like everyone else's; the table entries by a small copy each)
+    std::vector<uint8_t> h_tmp;
+    std::vector<mi355_packed_entry> entries;
+    entries.reserve(pk ? singles.size() : 0);
     for (size_t i : singles) {
         mi355_batch_item& it = items[i];
         size_t len = 0;
         int rc;
         const mi355_gzip_header h = gz.of(i);
+        if (pk) {
+            const size_t need = mi355_deflate_bound_ex(it.in_len, o->wrapper, h.hdr_len, 0);
+            if (host) {
+                if (h_tmp.size() < need) h_tmp.resize(need);
+            } else if (const int e = ensure_buf(c, &c->d_out, &c->d_out_cap, need)) {
+                return e;
+            }
+            it.out = host ? static_cast<void*>(h_tmp.data()) : static_cast<void*>(c->d_out);
+            it.out_cap = need;
+        }
         if (gz.gzip && host)
             rc = mi355_deflate_encode_gzip(c, reinterpret_cast<const uint8_t*>(it.in), it.in_len, o, h.hdr, h.hdr_len,
                                            reinterpret_cast<uint8_t*>(it.out), it.out_cap, &len);
@@ -591,8 +770,30 @@ int run_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, con
         bi.n_spec_single += single_spec[i];
         it.status = rc;
         it.out_len = (rc == MI355_OK || rc == MI355_E_OUT_TOO_SMALL) ? len : 0;
+        if (pk) {
+            const void* const src = it.out;
+            const uint64_t off = pk->tail, region = rc == MI355_OK ? pk->up(len) : 0;
+            it.out = nullptr;
+            it.out_cap = 0;
+            if (rc == MI355_OK && off + region > pk->cap) {
+                it.status = MI355_E_OUT_TOO_SMALL;
+            } else if (rc == MI355_OK && host) {
+                memcpy(pk->h_arena + off, src, len);
+                memset(pk->h_arena + off + len, 0, region - len);
+                it.out = pk->h_arena + off;
+            } else if (rc == MI355_OK) {
+                if (len) HIPCHK(c, hipMemcpyAsync(pk->d_arena + off, src, len, hipMemcpyDeviceToDevice, st));
+                if (region > len) HIPCHK(c, hipMemsetAsync(pk->d_arena + off + len, 0, region - len, st));
+                it.out = pk->d_arena + off;
+            }
+            pk->tail += region;
+            if (pk->d_table) {
+                entries.push_back(mi355_packed_entry{off, it.out_len, it.status, 0u});
+                HIPCHK(c, hipMemcpyAsync(pk->d_table + i, &entries.back(), sizeof(mi355_packed_entry), hipMemcpyHostToDevice, st));
+            }
+        }
+        if (rc == MI355_OK && it.status == MI355_OK) sum_out += len;
         if (rc == MI355_OK) {
-            sum_out += len;
             const mi355_deflate_info& in1 = c->info;
             sums.T += (uint32_t)in1.n_tokens;
             sums.nb += in1.n_blocks;
@@ -659,9 +860,102 @@ int batch_args_ok(mi355_deflate_ctx* c, const mi355_batch_item* items, size_t n_
     return MI355_OK;
 }
 
+// the checks of a packed call (nothing is written when one fails); *align: 0 becomes 4
+int packed_args_ok(mi355_deflate_ctx* c, const mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* o, const BatchHeaders& gz,
+                   const void* arena, size_t* align, bool device) {
+    if (!o || (!items && n_items)) return MI355_E_ARG;
+    if (o->wrapper < 0 || o->wrapper > 2) {
+        c->err = "packed batch: wrapper 0 (raw), 1 (zlib) or 2 (gzip)";
+        return MI355_E_ARG;
+    }
+    if (*align == 0) *align = 4;
+    if (*align < 4 || *align > 4096 || (*align & (*align - 1))) {
+        c->err = "packed batch: align is a power of two from 4 to 4096 (0: 4)";
+        return MI355_E_ARG;
+    }
+    if (!arena && n_items) {
+        c->err = "packed batch: no arena";
+        return MI355_E_ARG;
+    }
+    if (device && (reinterpret_cast<uintptr_t>(arena) & (*align - 1))) {
+        c->err = "packed batch: the device arena must be aligned to align";
+        return MI355_E_ARG;
+    }
+    if (gz.gzip) {  // (the rule of the _gzip entries)
+        if ((gz.n && !gz.h) || (gz.n > 1 && gz.n != n_items)) {
+            c->err = "batched gzip encode: n_hdrs is 0 (blank header), 1 (one for all) or n_items";
+            return MI355_E_ARG;
+        }
+        for (size_t i = 0; i < gz.n; i++)
+            if (!gz.h[i].hdr || gz.h[i].hdr_len == 0 || gz.h[i].hdr_len > 0xFFFF) {
+                c->err = "batched gzip encode: a header of 1 .. 65535 bytes per entry";
+                return MI355_E_ARG;
+            }
+    }
+    if (o->flush != MI355_FLUSH_FINISH) {
+        c->err = "batched encode: MI355_FLUSH_FINISH only";
+        return MI355_E_ARG;
+    }
+    for (size_t i = 0; i < n_items; i++)
+        if (!items[i].in && items[i].in_len) return MI355_E_ARG;
+    return MI355_OK;
+}
+
+int run_packed(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs,
+               size_t n_hdrs, uint8_t* d_arena, uint8_t* h_arena, size_t arena_cap, size_t align, mi355_packed_entry* d_table,
+               size_t* arena_used, void* hip_stream) {
+    const bool device = d_arena != nullptr || !h_arena;
+    const BatchHeaders gz = (opts && opts->wrapper == 2) ? BatchHeaders{hdrs, n_hdrs, true} : BatchHeaders{};
+    int rc = packed_args_ok(c, items, n_items, opts, gz, device ? static_cast<const void*>(d_arena) : h_arena, &align, device);
+    if (rc) return rc;
+    hipStream_t st = (device && hip_stream) ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    PackedOut pk{d_arena, h_arena, arena_cap, (uint32_t)align, d_table, 0, nullptr, {}};
+    rc = run_batch(c, items, n_items, opts, st, !device, device ? hip_stream : nullptr, gz, &pk);
+    // (the checks inside run_batch -- the options, a live shard -- fail before the first item is written)
+    if (rc == MI355_E_HIP || rc == MI355_E_UNSUPPORTED || rc == MI355_E_STATE || rc == MI355_E_ARG) return rc;
+    if (arena_used) *arena_used = (size_t)pk.tail;
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t mi355_deflate_batch_packed_bound(const mi355_batch_item* items, size_t n_items, int wrapper, const mi355_gzip_header* hdrs,
+                                        size_t n_hdrs, size_t align) {
+    if (align == 0) align = 4;
+    if ((!items && n_items) || align < 4 || align > 4096 || (align & (align - 1))) return 0;
+    const BatchHeaders gz = wrapper == 2 ? BatchHeaders{hdrs, n_hdrs, true} : BatchHeaders{};
+    if (gz.gzip && ((gz.n && !gz.h) || (gz.n > 1 && gz.n != n_items))) return 0;
+    size_t sum = 0;
+    for (size_t i = 0; i < n_items; i++) sum += align_up(mi355_deflate_bound_ex(items[i].in_len, wrapper, gz.of(i).hdr_len, 0), align);
+    return sum;
+}
+
+int mi355_deflate_encode_batch_packed(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
+                                      const mi355_gzip_header* hdrs, size_t n_hdrs, uint8_t* arena, size_t arena_cap, size_t align,
+                                      size_t* arena_used) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    if (!arena && n_items) {
+        c->err = "packed batch: no arena";
+        return MI355_E_ARG;
+    }
+    static uint8_t none;  // (an empty batch may come without an arena)
+    return run_packed(c, items, n_items, opts, hdrs, n_hdrs, nullptr, arena ? arena : &none, arena ? arena_cap : 0, align, nullptr,
+                      arena_used, nullptr);
+}
+
+int mi355_deflate_encode_batch_packed_device(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts,
+                                             const mi355_gzip_header* hdrs, size_t n_hdrs, void* d_arena, size_t arena_cap, size_t align,
+                                             mi355_packed_entry* d_table, size_t* arena_used, void* hip_stream) {
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    return run_packed(c, items, n_items, opts, hdrs, n_hdrs, static_cast<uint8_t*>(d_arena), nullptr, arena_cap, align, d_table, arena_used,
+                      hip_stream);
+}
 
 int mi355_deflate_encode_batch(mi355_deflate_ctx* c, mi355_batch_item* items, size_t n_items, const mi355_deflate_opts* opts) {
     DefaultGuard dg_;

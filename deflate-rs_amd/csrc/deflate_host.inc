@@ -544,13 +544,7 @@ void info_from_scalars(mi355_deflate_info* info, const DevScalars& s) {
     info->spec_repaired = 0;
     for (uint32_t k = 0; k < PIECES_MAX; k++) info->spec_repaired += s.n_fix[k];
 }
-// bytes of the stream with its frame (sync_tail: the call ends in a sync flush, the trailer is not written yet)
-size_t stream_bytes(uint64_t total_bits, uint32_t wrapper, size_t gz_len, bool sync_tail) {
-    const size_t body = (size_t)((total_bits + 7) / 8);
-    if (wrapper == 1) return body + (sync_tail ? 2 : 6);
-    if (wrapper == 2) return body + gz_len + (sync_tail ? 0 : 8);
-    return body;
-}
+// (bytes of the stream with its frame: stages.h stream_bytes, shared with kb_place)
 
 void launch_sort(mi355_deflate_ctx* c, hipStream_t st, uint32_t epochs, const uint8_t* d_in, uint32_t n32, const HashOverride& ov,
                  uint16_t* S, uint16_t* B, uint32_t e0, const SortInit* init = nullptr) {

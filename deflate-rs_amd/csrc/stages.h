@@ -1462,6 +1462,15 @@ MI355_HD uint64_t token_bits(uint32_t tok, const LLCodes& llc, const LLLens& lll
     return bits;
 }
 
+// bytes of the stream with its frame (sync_tail: the call ends in a sync flush, the trailer is not written yet); wrapper 0 raw,
+// 1 zlib (2 + 4), 2 gzip (the header's gz_len bytes + 8).  The host after the wait and kb_place (deflate_batch.inc) on the device.
+MI355_HD uint64_t stream_bytes(uint64_t total_bits, uint32_t wrapper, uint64_t gz_len, bool sync_tail) {
+    const uint64_t body = (total_bits + 7) / 8;
+    if (wrapper == 1) return body + (sync_tail ? 2 : 6);
+    if (wrapper == 2) return body + gz_len + (sync_tail ? 0 : 8);
+    return body;
+}
+
 // The flat grids of the batched kernels (deflate_batch.inc): a launch runs the workgroups of every item of a batch back to back,
 // and workgroup `bx` belongs to the last item i with pre[i] <= bx.  pre: the stage's running sum of workgroups per item,
 // n_items + 1 entries, pre[0] = 0, bx < pre[n_items]; an item without workgroups shares its entry with the item behind it.

@@ -110,6 +110,19 @@ class GzipHeader(C.Structure):
     _fields_ = [("hdr", C.c_char_p), ("hdr_len", C.c_size_t)]
 
 
+class PackedEntry(C.Structure):
+    """mi355_packed_entry: an item's place in the arena of a packed batch"""
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class PackedResult:
+    """What a packed batch call left: the arena, entries[i] = (off, len) of item i (off None for an item that is not OK; len is
+    exact either way), the items' statuses, the call's arena_used and its return code."""
+
+    def __init__(self, arena, entries, statuses, used, rc):
+        self.arena, self.entries, self.statuses, self.used, self.rc = arena, entries, statuses, used, rc
+
+
 class BatchInfo(C.Structure):
     """mi355_batch_info"""
     _fields_ = [("n_items", C.c_uint64), ("in_len", C.c_uint64), ("out_len", C.c_uint64), ("n_batched", C.c_uint32),
@@ -215,6 +228,15 @@ def load():
                                                   C.POINTER(GzipHeader), C.c_size_t]
     L.mi355_deflate_encode_batch_device_gzip.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
                                                          C.POINTER(GzipHeader), C.c_size_t, C.c_void_p]
+    L.mi355_deflate_batch_packed_bound.argtypes = [C.POINTER(BatchItem), C.c_size_t, C.c_int, C.POINTER(GzipHeader), C.c_size_t,
+                                                   C.c_size_t]
+    L.mi355_deflate_batch_packed_bound.restype = C.c_size_t
+    L.mi355_deflate_encode_batch_packed.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
+                                                    C.POINTER(GzipHeader), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                    C.POINTER(C.c_size_t)]
+    L.mi355_deflate_encode_batch_packed_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
+                                                           C.POINTER(GzipHeader), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                           C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
     _lib = L
     return L
 
@@ -239,6 +261,7 @@ EXPORTED = [
     "mi355_multi_stitch_info",
     "mi355_deflate_encode_batch", "mi355_deflate_encode_batch_device", "mi355_deflate_last_batch_info",
     "mi355_deflate_encode_batch_gzip", "mi355_deflate_encode_batch_device_gzip",
+    "mi355_deflate_batch_packed_bound", "mi355_deflate_encode_batch_packed", "mi355_deflate_encode_batch_packed_device",
 ]
 
 
@@ -469,6 +492,82 @@ class Context:
             self._batch_error(rc, items[: len(ins_pl)])
         return outs, [items[k].out_len for k in range(len(ins_pl))], [items[k].status for k in range(len(ins_pl))]
 
+    def _packed_result(self, arena, base, items, n, used, rc, check):
+        if rc != OK and check:
+            self._batch_error(rc, items[:n])
+        entries = [((items[k].out - base) if items[k].status == OK and items[k].out else None, items[k].out_len) for k in range(n)]
+        return PackedResult(arena, entries, [items[k].status for k in range(n)], used, rc)
+
+    def encode_batch_packed(self, datas, options=Compression.Default, wrapper=0, headers=None, align=4, compat=0, arena_cap=None,
+                            arena=None, check=True):
+        """Many host inputs in one batched call, all streams in ONE arena (mi355_deflate_encode_batch_packed).  Returns
+        (arena, [(off, len), ...]): item i's bytes are arena[off : off + len], exactly what encode(datas[i]) / encode_gzip gives;
+        off is a multiple of align and the regions are dense.  wrapper 2: headers as encode_batch_gzip.  arena_cap None: the
+        bound of packed_bound(); a smaller one is legal (mi355_deflate.h).  arena: a writable ctypes array to use instead of one
+        made here (then arena_cap defaults to its size); otherwise the arena comes back as a bytearray of the bytes used.
+        check False: no exception for a failing item, and the return value is the PackedResult."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(wrapper, compat, 0)
+        datas = [bytes(d) for d in datas]
+        n = len(datas)
+        arr, n_hdrs, keep, _ = self._gzip_headers(headers if wrapper == 2 else None, n)
+        items = (BatchItem * max(n, 1))()
+        for k, d in enumerate(datas):
+            items[k].in_ = C.cast(C.c_char_p(d), C.c_void_p) if d else C.c_void_p(0)
+            items[k].in_len = len(d)
+        own = arena is None
+        if own:
+            if arena_cap is None:
+                arena_cap = L.mi355_deflate_batch_packed_bound(items, n, wrapper, arr, n_hdrs, align)
+            arena = (C.c_uint8 * max(arena_cap, 1))()
+        elif arena_cap is None:
+            arena_cap = C.sizeof(arena)
+        used = C.c_size_t(0)
+        rc = L.mi355_deflate_encode_batch_packed(self._h, items, n, C.byref(o), arr, n_hdrs, C.cast(arena, C.c_void_p), arena_cap,
+                                                 align, C.byref(used))
+        res = self._packed_result(arena, C.addressof(arena), items, n, used.value, rc, check)
+        if own:
+            res.arena = bytearray(memoryview(arena)[: min(used.value, arena_cap)])
+        return (res.arena, res.entries) if check else res
+
+    def encode_batch_packed_device(self, ins, arena=None, options=Compression.Default, wrapper=0, headers=None, align=4, compat=0,
+                                   arena_cap=None, table=None, stream=0, check=True):
+        """Device inputs in one batched call, all streams in ONE device arena (mi355_deflate_encode_batch_packed_device).  ins: torch
+        tensors on this context's device or (pointer, length) pairs; arena: a uint8 tensor or such a pair, aligned to align (None:
+        a tensor of packed_bound() bytes, made here); table: None, or a device buffer of 24 bytes per item (tensor or pair) that
+        receives the items' mi355_packed_entry.  Returns a PackedResult (arena = the tensor or pair).  check: raise DeflateError
+        naming the first failing index."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(wrapper, compat, 0)
+
+        def ptr_len(x):
+            if isinstance(x, tuple):
+                return int(x[0]), int(x[1])
+            return int(x.data_ptr()), int(x.numel() * x.element_size())
+        ins_pl = [ptr_len(x) for x in ins]
+        n = len(ins_pl)
+        arr, n_hdrs, keep, _ = self._gzip_headers(headers if wrapper == 2 else None, n)
+        items = (BatchItem * max(n, 1))()
+        for k, (ip, ln) in enumerate(ins_pl):
+            items[k].in_ = C.c_void_p(ip if ln else 0)
+            items[k].in_len = ln
+        if arena is None:
+            import torch
+            dev = ins[0].device if ins and not isinstance(ins[0], tuple) else torch.device("cuda", 0)
+            cap = arena_cap if arena_cap is not None else L.mi355_deflate_batch_packed_bound(items, n, wrapper, arr, n_hdrs, align)
+            arena = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            arena_cap = cap
+        ap, alen = ptr_len(arena)
+        if arena_cap is None:
+            arena_cap = alen
+        if table is not None and ptr_len(table)[1] < C.sizeof(PackedEntry) * n:
+            raise ValueError("table: %d bytes per item" % C.sizeof(PackedEntry))
+        used = C.c_size_t(0)
+        rc = L.mi355_deflate_encode_batch_packed_device(self._h, items, n, C.byref(o), arr, n_hdrs, C.c_void_p(ap), arena_cap, align,
+                                                        C.c_void_p(ptr_len(table)[0] if table is not None else 0), C.byref(used),
+                                                        C.c_void_p(stream))
+        return self._packed_result(arena, ap, items, n, used.value, rc, check)
+
     def batch_info(self):
         """mi355_deflate_last_batch_info as a dict"""
         i = BatchInfo()
@@ -590,6 +689,28 @@ def deflate_bytes_gzip_batch_conf(datas, options, headers=None, ctx=None):
 
 def deflate_bytes_gzip_batch(datas, ctx=None):
     return deflate_bytes_gzip_batch_conf(datas, Compression.Default, None, ctx)
+
+
+# ---- ... with all outputs in one arena (mi355_deflate_encode_batch_packed) ------------------------
+def packed_bound(lens, wrapper=0, headers=None, align=4):
+    """mi355_deflate_batch_packed_bound: the arena that always suffices for inputs of these lengths (no GPU involved).
+    headers (wrapper 2): None, one bytes, or one per input."""
+    lens = [int(x) for x in lens]
+    arr, n_hdrs, keep, _ = Context._gzip_headers(headers if wrapper == 2 else None, len(lens))
+    items = (BatchItem * max(len(lens), 1))()
+    for k, ln in enumerate(lens):
+        items[k].in_len = ln
+    return load().mi355_deflate_batch_packed_bound(items, len(lens), wrapper, arr, n_hdrs, align)
+
+
+def deflate_bytes_batch_packed_conf(datas, options, wrapper=0, headers=None, align=4, ctx=None):
+    """deflate_bytes_conf / _zlib_conf / _gzip_conf (wrapper 0 / 1 / 2) of every input, in one batch and one arena:
+    (arena, [(off, len), ...])"""
+    return (ctx or default_context()).encode_batch_packed(datas, options, wrapper=wrapper, headers=headers, align=align)
+
+
+def deflate_bytes_batch_packed(datas, ctx=None):
+    return deflate_bytes_batch_packed_conf(datas, Compression.Default, ctx=ctx)
 
 
 # ---- the reference's Write encoders (src/writer.rs) ---------------------------------------------

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MI355_DEFLATE_VERSION 100 /* 0.1.0 */
+#define MI355_DEFLATE_VERSION 101 /* 0.1.1: the packed batch */
 
 #define MI355_OK 0
 #define MI355_E_ARG (-1)           /* null pointer / bad option */
@@ -308,6 +308,55 @@ int mi355_deflate_encode_batch_gzip(mi355_deflate_ctx* ctx, mi355_batch_item* it
 int mi355_deflate_encode_batch_device_gzip(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
                                            const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs,
                                            void* hip_stream);
+
+/* ---- batched encode into one packed arena ---------------------------------------------------------
+ * The batch above with another way of handing the bytes back: all streams back to back in ONE caller-supplied arena, at
+ * offsets worked out on the device from the streams' exact lengths, so that the arena needs to be only as large as the
+ * output is.  The items are mi355_batch_item: `in` and `in_len` are read, `out` and `out_cap` are ignored on entry; on
+ * return `out` is the item's address inside the arena (NULL for an item that is not MI355_OK), `out_len` its exact
+ * length and `status` its status.
+ * Wrapper and headers: opts->wrapper is 0 (raw), 1 (zlib) or 2 (gzip); hdrs / n_hdrs are read for wrapper 2 only, with the
+ *   0 / 1 / n_items rule of the _gzip entries above.  The other checks of the call are those of mi355_deflate_encode_batch
+ *   (MI355_FLUSH_FINISH only; lazy_if_less_than < 3 with Lazy is MI355_E_UNSUPPORTED; a live shard is MI355_E_STATE).  A
+ *   call that fails its checks writes no item, no arena byte and leaves *arena_used alone.
+ * align: a power of two from 4 to 4096; 0 means 4; anything else is MI355_E_ARG.  The device arena must be aligned to
+ *   `align`; the host arena may have any address.
+ * Bytes: item i's out_len bytes at out are byte for byte what mi355_deflate_encode / mi355_deflate_encode_gzip gives for
+ *   that item alone -- whatever the other items, their order or number, the way the batch is cut into launch sets, and
+ *   whatever align is.
+ * Layout: every OK item owns the region [off, off + align_up(len, align)) of the arena, off a multiple of align; the
+ *   regions are disjoint and dense, pad bytes inside a region are zero, and *arena_used is the sum of align_up(len, align)
+ *   over the OK items = the end of the last region.  No order of the regions is promised (today: the items of the
+ *   batched kernels in item order, then those of the one-input path in item order); the table tells.  Arena contents at or
+ *   beyond *arena_used are unspecified; nothing is ever written at or beyond arena_cap.
+ * Capacity: arena_cap >= mi355_deflate_batch_packed_bound(...) always succeeds; the bound is the sum of
+ *   align_up(mi355_deflate_bound_ex(in_len_i, wrapper, hdr_len_i, 0), align), computed on the host without a GPU (hdr_len_i:
+ *   0 unless wrapper is 2; 10, the blank header, with n_hdrs 0).  A smaller arena is legal: offsets are assigned as if it
+ *   were unbounded, and an item whose region would end beyond arena_cap is not written -- it gets MI355_E_OUT_TOO_SMALL
+ *   and its exact out_len; the call then returns MI355_E_OUT_TOO_SMALL and *arena_used holds the bytes the whole batch
+ *   needs.  The items that fit are complete and valid, and a second call with arena_cap = *arena_used succeeds.
+ * Failing items: MI355_E_REF_PANIC under MI355_COMPAT_Q13 takes no bytes, like the overflow above, and does not disturb
+ *   its neighbours.  The call returns the status of the first failing item, as mi355_deflate_encode_batch does.
+ * d_table (device memory, n_items entries, may be NULL): entry i = {off, len, status} of items[i], for a caller whose
+ *   next kernel reads the arena; off = out - arena for an OK item, and the offset the item was assigned (nothing is
+ *   written there) for one that is not.  It is complete when the call returns, which is after the stream has drained.
+ * mi355_deflate_last_batch_info, mi355_deflate_last_info, mi355_deflate_last_blocks and the routing of the items
+ * (the batched kernels or the one-input path, MI355_CFG_BATCH_BYTES): as with mi355_deflate_encode_batch. */
+typedef struct {
+    uint64_t off, len; /* the item's first byte in the arena; its exact length */
+    int32_t status;    /* MI355_OK or the item's MI355_E_* */
+    uint32_t reserved; /* 0 */
+} mi355_packed_entry;  /* 24 bytes */
+
+size_t mi355_deflate_batch_packed_bound(const mi355_batch_item* items, size_t n_items, int wrapper,
+                                        const mi355_gzip_header* hdrs, size_t n_hdrs, size_t align);
+int mi355_deflate_encode_batch_packed(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                                      const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs,
+                                      uint8_t* arena, size_t arena_cap, size_t align, size_t* arena_used);
+int mi355_deflate_encode_batch_packed_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items,
+                                             const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs,
+                                             void* d_arena, size_t arena_cap, size_t align, mi355_packed_entry* d_table,
+                                             size_t* arena_used, void* hip_stream);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range

@@ -66,6 +66,12 @@ extern "C" {
     fn mi355_deflate_encode_batch_device(ctx: *mut Ctx, items: *mut Mi355BatchItem, n_items: usize, opts: *const Mi355Opts,
                                          hip_stream: *mut std::ffi::c_void) -> c_int;
     fn mi355_deflate_last_batch_info(ctx: *mut Ctx, info: *mut std::ffi::c_void) -> c_int;
+    // ... with all streams in one arena (include/mi355_deflate.h, "batched encode into one packed arena")
+    fn mi355_deflate_batch_packed_bound(items: *const Mi355BatchItem, n_items: usize, wrapper: c_int, hdrs: *const std::ffi::c_void,
+                                        n_hdrs: usize, align: usize) -> usize;
+    fn mi355_deflate_encode_batch_packed(ctx: *mut Ctx, items: *mut Mi355BatchItem, n_items: usize, opts: *const Mi355Opts,
+                                         hdrs: *const std::ffi::c_void, n_hdrs: usize, arena: *mut u8, arena_cap: usize, align: usize,
+                                         arena_used: *mut usize) -> c_int;
     fn mi355_device_count() -> c_int; // (the shim links libmi355deflate.so only: no HIP symbol is named from Rust)
 }
 
@@ -224,6 +230,43 @@ pub fn deflate_bytes_batch_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], o
 /// deflate_bytes_zlib_conf (src/lib.rs:182-198) of every input, in one batched call
 pub fn deflate_bytes_zlib_batch_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O) -> Vec<Vec<u8>> {
     batch(inputs, c_opts(options.into(), 1))
+}
+/// The streams of a batch in one buffer: item i is `arena[ranges[i].clone()]`; every range starts on a multiple of `align`, the
+/// ranges are dense and the bytes between them are zero (include/mi355_deflate.h, mi355_deflate_encode_batch_packed).
+pub struct PackedBatch {
+    pub arena: Vec<u8>,
+    pub ranges: Vec<std::ops::Range<usize>>,
+}
+fn batch_packed(inputs: &[&[u8]], o: Mi355Opts, align: usize) -> PackedBatch {
+    unsafe {
+        let mut items: Vec<Mi355BatchItem> = inputs
+            .iter()
+            .map(|i| Mi355BatchItem { input: i.as_ptr(), in_len: i.len(), out: std::ptr::null_mut(), out_cap: 0, out_len: 0, status: 0 })
+            .collect();
+        let bound = mi355_deflate_batch_packed_bound(items.as_ptr(), items.len(), o.wrapper as c_int, std::ptr::null(), 0, align);
+        assert!(inputs.is_empty() || bound > 0, "mi355_deflate_batch_packed_bound: align is a power of two from 4 to 4096");
+        let mut arena: Vec<u8> = Vec::with_capacity(bound.max(1));
+        let mut used = 0usize;
+        let rc = mi355_deflate_encode_batch_packed(std::ptr::null_mut(), items.as_mut_ptr(), items.len(), &o, std::ptr::null(), 0,
+                                                   arena.as_mut_ptr(), bound, align, &mut used);
+        assert!(rc == 0, "mi355_deflate_encode_batch_packed failed: {}", rc);
+        arena.set_len(used);
+        let base = arena.as_ptr() as usize;
+        let ranges = items.iter().map(|it| (it.out as usize - base)..(it.out as usize - base + it.out_len)).collect();
+        PackedBatch { arena, ranges }
+    }
+}
+/// deflate_bytes_conf (src/lib.rs:137-147) of every input, in one batched call and one buffer (4-byte aligned items)
+pub fn deflate_bytes_batch_packed_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O) -> PackedBatch {
+    batch_packed(inputs, c_opts(options.into(), 0), 4)
+}
+/// ... with the items' first bytes on multiples of `align` (a power of two from 4 to 4096)
+pub fn deflate_bytes_batch_packed_aligned_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O, align: usize) -> PackedBatch {
+    batch_packed(inputs, c_opts(options.into(), 0), align)
+}
+/// deflate_bytes_zlib_conf (src/lib.rs:182-198) of every input, in one batched call and one buffer
+pub fn deflate_bytes_zlib_batch_packed_conf<O: Into<CompressionOptions>>(inputs: &[&[u8]], options: O) -> PackedBatch {
+    batch_packed(inputs, c_opts(options.into(), 1), 4)
 }
 /// src/lib.rs:242-267
 #[cfg(feature = "gzip")]

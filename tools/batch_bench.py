@@ -7,7 +7,14 @@ ends in a synchronise.  --wrapper 1 / 2 times the same workloads with zlib / gzi
 mi355_deflate_encode_device_gzip, the batch through mi355_deflate_encode_batch_device_gzip; profiles/batch_bench_gzip.json holds
 a run of 2 and of 1 from one session).  --workloads picks the workloads: by default the four of generated text, and with a level
 without a hash (rle, huffman_only) also 256x64KiB_runs, rows of runs of equal bytes (the generated text has no run longer than 5).
-Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--wrapper W] [--levels L,L] [--workloads W,W] [--out FILE]"""
+--packed times the packed batch instead (all streams in one arena, mi355_deflate_encode_batch_packed[_device]) beside the
+existing batch entries on the same workloads, the C entries called directly on prepared item arrays: device-resident packed
+against mi355_deflate_encode_batch_device, and the host entries on pageable memory against each other; the runs of a pair
+alternate.  Levels: Default and Fast, and RLE on the rows of runs.  Per pair the best of --reps, the baseline's spread
+(max - min) and the allowance the device-resident packed call is held against: the baseline's best + two short launches
+(LAUNCH_US each: kb_place and the clear) + that spread.  Per workload also packed_bound, arena_used and the input bytes.
+Writes profiles/batch_bench_packed.json unless --out says otherwise.
+Prints ONE JSON line.  python tools/batch_bench.py [--reps N] [--wrapper W] [--levels L,L] [--workloads W,W] [--packed] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -73,6 +80,91 @@ def timed(fn, reps):
     return best
 
 
+LAUNCH_US = 4.8  # a short launch such as k_plan
+
+
+def packed_bench(a, ctx, L):
+    """--packed: see the module's docstring"""
+    w = a.wrapper
+    names = [x for x in a.workloads.split(",") if x] if a.workloads else list(TEXT_WORKLOADS) + [RUNS_WORKLOAD]
+    res = {"metric": "packed batch against the batch entries (best of %d, alternating runs)" % a.reps, "wrapper": w,
+           "launch_us": LAUNCH_US, "workloads": {}}
+    for name, datas in workloads(names).items():
+        n = len(datas)
+        nbytes = sum(map(len, datas))
+        ins = [torch.frombuffer(bytearray(d), dtype=torch.uint8).cuda() for d in datas]
+        hlen = len(da.BLANK_GZIP_HEADER) if w == 2 else 0
+        caps = [L.mi355_deflate_bound_ex(len(d), w, hlen, 0) for d in datas]
+        outs = [torch.empty(cap, dtype=torch.uint8, device="cuda") for cap in caps]
+        bound = da.packed_bound([len(d) for d in datas], w, None, 4)
+        arena = torch.empty(bound, dtype=torch.uint8, device="cuda")
+        table = torch.empty(24 * n, dtype=torch.uint8, device="cuda")
+        h_outs = [(C.c_uint8 * cap)() for cap in caps]
+        h_arena = (C.c_uint8 * bound)()
+        torch.cuda.synchronize()
+        d_items, p_items, h_items, hp_items = ((da.BatchItem * n)() for _ in range(4))
+        for k, d in enumerate(datas):
+            for it in (d_items, p_items):
+                it[k].in_, it[k].in_len = C.c_void_p(ins[k].data_ptr()), len(d)
+            for it in (h_items, hp_items):
+                it[k].in_, it[k].in_len = C.cast(C.c_char_p(d), C.c_void_p), len(d)
+            d_items[k].out, d_items[k].out_cap = C.c_void_p(outs[k].data_ptr()), caps[k]
+            h_items[k].out, h_items[k].out_cap = C.cast(h_outs[k], C.c_void_p), caps[k]
+        row = {"items": n, "bytes": nbytes, "packed_bound": bound, "item_bounds": sum(caps)}
+        levels = ["default", "fast"] if name != RUNS_WORKLOAD else ["rle"]
+        for lvl in levels:
+            o_c = da.CompressionOptions.from_(LEVELS[lvl]).to_c(w, 0, 0)
+            used = C.c_size_t(0)
+
+            def dev_base():
+                if w == 2:
+                    return L.mi355_deflate_encode_batch_device_gzip(ctx._h, d_items, n, C.byref(o_c), None, 0, None)
+                return L.mi355_deflate_encode_batch_device(ctx._h, d_items, n, C.byref(o_c), None)
+
+            def dev_packed():
+                return L.mi355_deflate_encode_batch_packed_device(ctx._h, p_items, n, C.byref(o_c), None, 0, C.c_void_p(arena.data_ptr()),
+                                                                  bound, 4, C.c_void_p(table.data_ptr()), C.byref(used), None)
+
+            def host_base():
+                if w == 2:
+                    return L.mi355_deflate_encode_batch_gzip(ctx._h, h_items, n, C.byref(o_c), None, 0)
+                return L.mi355_deflate_encode_batch(ctx._h, h_items, n, C.byref(o_c))
+
+            def host_packed():
+                return L.mi355_deflate_encode_batch_packed(ctx._h, hp_items, n, C.byref(o_c), None, 0, C.cast(h_arena, C.c_void_p), bound, 4,
+                                                           C.byref(used))
+            fns = {"batch_device": dev_base, "packed_device": dev_packed, "batch_host": host_base, "packed_host": host_packed}
+            times = {k: [] for k in fns}
+            for k, fn in fns.items():  # (warm: this shape's allocations, the code objects)
+                assert fn() == 0, k
+            torch.cuda.synchronize()
+            for _ in range(a.reps):
+                for k, fn in fns.items():
+                    t0 = time.perf_counter()
+                    rc = fn()
+                    ms = (time.perf_counter() - t0) * 1e3  # (every entry returns after its stream has drained)
+                    assert rc == 0, (k, rc)
+                    times[k].append(ms)
+            # the same bytes both ways, item by item
+            got = arena.cpu().numpy().tobytes()
+            for k in range(0, n, max(n // 16, 1)):
+                off = p_items[k].out - arena.data_ptr()
+                assert got[off:off + p_items[k].out_len] == outs[k][:d_items[k].out_len].cpu().numpy().tobytes(), k
+                assert bytes(h_arena[hp_items[k].out - C.addressof(h_arena):][:hp_items[k].out_len]) == bytes(h_outs[k][:h_items[k].out_len]), k
+            base, spread = min(times["batch_device"]), max(times["batch_device"]) - min(times["batch_device"])
+            allowance = base + 2 * LAUNCH_US / 1e3 + spread
+            row[lvl] = {
+                "batch_device_ms": round(base, 4), "batch_device_spread_ms": round(spread, 4),
+                "packed_device_ms": round(min(times["packed_device"]), 4), "allowance_ms": round(allowance, 4),
+                "packed_device_within_allowance": min(times["packed_device"]) <= allowance,
+                "batch_host_ms": round(min(times["batch_host"]), 4), "packed_host_ms": round(min(times["packed_host"]), 4),
+                "host_batch_over_packed": round(min(times["batch_host"]) / min(times["packed_host"]), 3),
+                "arena_used": used.value, "runs_ms": {k: [round(x, 4) for x in v] for k, v in times.items()},
+            }
+        res["workloads"][name] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -81,7 +173,17 @@ def main():
     ap.add_argument("--workloads", default=None, help="comma-separated: %s, %s (default: the text ones, and the runs with a level "
                     "without a hash)" % (", ".join(TEXT_WORKLOADS), RUNS_WORKLOAD))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--packed", action="store_true", help="the packed batch beside the batch entries (profiles/batch_bench_packed.json)")
     a = ap.parse_args()
+    if a.packed:
+        ctx = da.Context(0)
+        res = packed_bench(a, ctx, da.load())
+        ctx.close()
+        line = json.dumps(res)
+        print(line)
+        with open(a.out or os.path.join(ROOT, "profiles", "batch_bench_packed.json"), "w") as f:
+            f.write(line + "\n")
+        return
     levels = [x for x in a.levels.split(",") if x]
     for x in levels:
         if x not in LEVELS:
