@@ -66,7 +66,7 @@ __global__ __launch_bounds__(M3T) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t e = local / split, part = local % split;
     const SegEnds sg{it.seg_ends, 1u};
     const int aligned16 = (reinterpret_cast<uintptr_t>(it.in) & 15) == 0 ? 1 : 0;
-    uint32_t* const ms = split == 1 ? it.tokbuf : nullptr;
+    uint32_t* const ms = split == 1 ? walk_borrows(it.tokbuf, it.K0) : nullptr;  // (as launch_walk)
     uint32_t* const mqs = (HAS_Q && split == 1) ? it.dtok : nullptr;
     uint32_t* const Mq = HAS_Q ? it.Mq : nullptr;
     if (MI355_SWZ_BANKS && __builtin_amdgcn_readfirstlane((int)it.B[(size_t)e * BSTRIDE + WINDOW_SIZE + 2]))

@@ -336,7 +336,7 @@ Workspace carve(uint8_t* base, uint64_t n, bool need_q, size_t m = 1, size_t gz_
         cnt = (cnt + FAN - 1) / FAN;
         usize *= FAN;
     }
-    w.tokbuf = c.take<uint32_t>((size_t)w.K0 * SEG + 64);
+    w.tokbuf = c.take<uint32_t>((size_t)w.K0 * TOK_SLOT + 64);
     w.cnt = c.take<uint32_t>((size_t)w.K0 + 64);
     w.base = c.take<uint32_t>((size_t)w.K0 + 64);
     w.scan_part = c.take<uint32_t>((size_t)w.K0 / 1024 + 2 + 2 * PIECES_MAX);
@@ -580,12 +580,13 @@ void launch_walk(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint
     const uint32_t split = plan.split, cq = cfg_cq(cfg);
     const bool has_q = cfg_has_q(cfg);
     // (k_match3 borrows the token arrays, which nothing has written yet, for the results in sorted order: 4 B per position each)
-    uint32_t* const ms = split == 1 ? w.tokbuf : nullptr;
+    uint32_t* const borrowed = walk_borrows(w.tokbuf, w.K0);
+    uint32_t* const ms = split == 1 ? borrowed : nullptr;
     uint32_t* const mqs = split == 1 ? w.dtok : nullptr;
     if (MI355_SWZ_BANKS && ne * split <= M3_BOTH_UNITS) {  // small: both tables in one launch
         const bool single = plan.single;
         const uint32_t sp = single ? split * 2 : split;
-        uint32_t* const ms1 = sp == 1 ? w.tokbuf : nullptr;
+        uint32_t* const ms1 = sp == 1 ? borrowed : nullptr;
         uint32_t* const mqs1 = sp == 1 ? w.dtok : nullptr;
 #define MI355_BOTH(Q, SNG, mq, mqs, cqv)                                                                                       \
     hipLaunchKernelGGL((k_match3_both<Q, SNG>), dim3(ne * sp), dim3(M3T), 0, st, d_in, n32, S, w.buckets, w.M, mq, cfg.checks, cqv, \

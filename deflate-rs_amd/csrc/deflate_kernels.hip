@@ -11,7 +11,7 @@
 //   adv    u16[n]      restart step length from every position                   2 B/byte
 //   J      u16[n]      scratch of the per-segment exit sweep                     2 B/byte
 //   X[l]   u16[K_l*ZONE]  exit tables per level (an exit lies less than MAX_JUMP beyond its unit), E[l] u32[K_l] entry positions
-//   tokbuf u32[K*SEG]  tokens per segment, dtok u32[T] tokens in stream order    4 + 4 B/byte
+//   tokbuf u32[K*TOK_SLOT]  tokens per segment, dtok u32[T] tokens in stream order    5 + 4 B/byte
 //   per block: ll_freq u32[4][288], d_freq u32[4][32] (a histogram per quarter of the block), BlockHeader, BlockPlan, bstart
 // All integer work; the bound is vector-ALU issue / LDS in k_match3 and latency or HBM elsewhere.
 #include <hip/hip_runtime.h>
@@ -118,6 +118,16 @@ struct DevState {
 __device__ __forceinline__ bool spec_failed(const DevScalars* sc) { return (reinterpret_cast<const DevState*>(sc)->spec_bad | sc->q1_cancel) != 0; }
 
 constexpr uint32_t SEG = 1024;  // positions per level-0 segment
+// A segment's tokens are those of the steps that START in it, and the last step's deferred literals and match may lie behind its
+// end: 1023 literal steps and a lazy step at its last position with up to 255 deferrals (lazy_if_less_than 258) are 1279 tokens.
+// The slot is 1280 words -- 16-byte aligned, which is what k_compact's reads of sixteen bytes need.
+constexpr uint32_t TOK_SLOT = SEG + 256;  // words per segment in tokbuf
+static_assert(TOK_SLOT >= (SEG - 1) + 255 + 1 && TOK_SLOT % 4 == 0, "SEG - 1 literal steps, 255 deferrals and a match; sixteen-byte reads in k_compact");
+// k_match3 borrows tokbuf, which nothing has written yet, for its results in sorted order, a word per position: the END of it,
+// position j at word K0 * (TOK_SLOT - SEG) + j.  Where a walk runs beside the parse of the segments in front of it (the pieces of
+// the streamed call), segment k's slot ends at (k + 1) * TOK_SLOT <= K0 * (TOK_SLOT - SEG) + s * SEG for every k < s <= K0: in
+// front of the word of the walk's first position, in segment s.  From word 0 on, the walk's results lay in those slots.
+__host__ __device__ inline uint32_t* walk_borrows(uint32_t* tokbuf, uint32_t K0) { return tokbuf + (size_t)K0 * (TOK_SLOT - SEG); }
 #ifndef MI355_ADV_STRAIGHT
 #define MI355_ADV_STRAIGHT 1  // (k_adv 0.22 -> 0.14 ms: parse 0.577 -> 0.494 ms)
 #endif
@@ -2261,8 +2271,8 @@ __device__ __forceinline__ void k_compact_body(uint32_t bx_, uint32_t K, const u
     if (k >= K || spec_failed(sc)) return;
     uint32_t lane = threadIdx.x & 63;
     uint32_t c = cnt[k], b = base[k];
-    const uint32_t* src = tokbuf + k * SEG;
-    // (sixteen bytes a lane -- the slot is 4 KiB aligned, the dense array takes them at any dword --: with four bytes a lane the copy
+    const uint32_t* src = tokbuf + k * TOK_SLOT;
+    // (sixteen bytes a lane -- the slot is 16-byte aligned, the dense array takes them at any dword --: with four bytes a lane the copy
     // ran at 4.4 TB/s and looked bound by memory; 53 -> 38 us)
     const uint32_t c4 = c & ~3u;
     for (uint32_t i = 4 * lane; i < c4; i += 256) *reinterpret_cast<uint4*>(dtok + b + i) = *reinterpret_cast<const uint4*>(src + i);
@@ -2291,7 +2301,7 @@ __device__ uint32_t token_start(uint32_t t, uint32_t K, const uint32_t* base, co
     }
     if (seg) *seg = lo;
     const uint32_t m = t - base[lo];
-    const uint32_t* tk = tokbuf + (uint64_t)lo * SEG;
+    const uint32_t* tk = tokbuf + (uint64_t)lo * TOK_SLOT;
     uint32_t cov = 0;
     // (a segment's tokens before t -- up to 1023 on noise --, fetched together: a load a round was a memory latency a round,
     // sixteen in a row where every byte is a token)
@@ -2300,6 +2310,8 @@ __device__ uint32_t token_start(uint32_t t, uint32_t K, const uint32_t* base, co
     for (uint32_t r = 0; r < SEG / 64; r++) tv[r] = lane + 64 * r < m ? tk[lane + 64 * r] : 0u;
 #pragma unroll
     for (uint32_t r = 0; r < SEG / 64; r++) cov += lane + 64 * r < m ? tok_cover(tv[r]) : 0u;
+    // (a segment that ends in a chain of deferrals holds more than SEG tokens: the rest of its slot, the same for the whole wave)
+    for (uint32_t i = SEG + lane; i < m; i += 64) cov += tok_cover(tk[i]);
 #pragma unroll
     for (int off = 32; off; off >>= 1) cov += __shfl_xor(cov, off, 64);
     return E0[lo] + cov;
@@ -2338,7 +2350,7 @@ __global__ __launch_bounds__(64) void k_seg_tokens(SegEnds sg, uint32_t K, const
         return;
     }
     uint32_t pos = E0[k], c = 0, nk = cnt[k];
-    const uint32_t* tk = tokbuf + (uint64_t)k * SEG;
+    const uint32_t* tk = tokbuf + (uint64_t)k * TOK_SLOT;
     while (pos < e && c < nk) pos += tok_cover(tk[c++]);
     tend[i] = base[k] + c;
 }
@@ -2558,7 +2570,7 @@ __device__ __forceinline__ void k_small_fix_body(uint32_t bx_, const uint8_t* in
             const uint32_t t1 = t0 + MAX_BUFFER_LENGTH - 1;
             uint32_t seg = 0;
             const uint32_t tp = token_start(t1, K, s_base, E0, tokbuf, lane, &seg);
-            const uint32_t tk = tokbuf[(uint64_t)seg * SEG + (t1 - s_base[seg])];
+            const uint32_t tk = tokbuf[(uint64_t)seg * TOK_SLOT + (t1 - s_base[seg])];
             if (tp < WINDOW_SIZE && lane == 0) {  // (Q1, lz77.rs:628-638)
                 sc->b0_full = 1;
                 sc->b0_last_tok = tk;

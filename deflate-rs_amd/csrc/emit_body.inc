@@ -7,7 +7,7 @@
     // (runup0: the first segment has data in front of it as well -- a range of a sharded or long encode with its history --
     // and finds its entry like the others; without it the first segment starts at the stream's true entry, position 0)
     const uint32_t w0 = (SPEC && (k > 0 || runup0)) ? SPEC_W : 0u;
-    const uint64_t a0 = k * SEG;  // the segment proper: its tokens go to slot k of tokbuf
+    const uint64_t a0 = k * SEG;  // the segment proper: its tokens go to slot k of tokbuf (TOK_SLOT words)
     const uint64_t a = a0 - w0, b = a0 + SEG < n ? a0 + SEG : n;  // (everything below is relative to a: the start of the run-up)
     const uint32_t len = (uint32_t)(b - a);
     if (!STEPS) {   // (fetched together: a load per round of a loop is a memory latency per round)
@@ -129,7 +129,7 @@
     }
     wave_lds_fence();
     const uint32_t np = EMIT_NP;
-    uint32_t* out = tokbuf + a0;
+    uint32_t* out = tokbuf + k * TOK_SLOT;  // (up to TOK_SLOT - 1 tokens: SEG - 1 literal steps and the longest lazy step)
     // (32-bit positions relative to the first byte the wave holds: tables, input and the end of the data)
     const uint64_t sbase = (uint64_t)pos0 + a;
     const uint32_t* const Ms = M + sbase;

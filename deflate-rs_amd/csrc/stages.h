@@ -44,7 +44,8 @@ enum : uint32_t {
     NUM_LL = 286,               // huffman_table.rs:14
     NUM_DIST = 30,              // huffman_table.rs:10
     END_OF_BLOCK = 256,         // huffman_table.rs:28
-    MAX_JUMP = 520,             // bound on next(j)-j: <=257 lazy deferrals + 258 match bytes
+    MAX_JUMP = 520,             // bound on next(j)-j, a loose one: the lengths of a chain rise strictly from 3 to 258, so a step has
+                                // at most 255 lazy deferrals, and 255 + 258 match bytes = 513
     ZONE = 576,                 // entry zone of a segment (>= MAX_JUMP, multiple of 64)
 };
 

@@ -419,42 +419,8 @@ void stage_parse_hier(Sim& s, uint32_t S, uint32_t G) {
     if (toks != s.tokens) s.hier_mismatch = 1;
 }
 
-struct BitSink {
-    std::vector<uint8_t>& out;
-    void put(uint64_t bitpos, uint64_t bits, uint32_t nbits) {
-        for (uint32_t i = 0; i < nbits; i++)
-            if ((bits >> i) & 1) out[(bitpos + i) >> 3] |= (uint8_t)(1u << ((bitpos + i) & 7));
-    }
-};
-
-}  // namespace
-
-extern "C" {
-
-// encode_lengths_rle (the reference's state machine) against encode_lengths_runs (run by run, what
-// k_block_header does): 0 = same symbols, else 1 + the index of the first difference
-int hostsim_rle_forms_agree(const uint8_t* lens, uint32_t n) {
-    std::vector<uint16_t> a(n + 8), b(n + 8);
-    uint32_t freqs[19] = {0};
-    const uint32_t na = encode_lengths_rle(lens, n, a, freqs);
-    const uint32_t nb = encode_lengths_runs(lens, n, b);
-    if (na != nb) return 1 + (int)std::min(na, nb);
-    for (uint32_t i = 0; i < na; i++)
-        if (a[i] != b[i]) return 1 + (int)i;
-    return 0;
-}
-
-struct hostsim_block {
-    uint32_t btype, bfinal, ntok;
-    uint64_t in_bytes, bit_start;
-};
-
-// returns 0 ok; -3 = reference would panic (Q13 slice out of range); fills *flags with bit0 =
-// Q1 override used, bit1 = Q13 shifted stored source used, bit2 = hierarchical path mismatch
-int hostsim_encode(const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy_lt, uint32_t matching_type,
-                   uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t* flags, hostsim_block* blocks,
-                   uint64_t blocks_cap, uint64_t* n_blocks, uint32_t seg, uint32_t fan) {
-    Sim s;
+// the tables and the tokens of a call: links, match table(s), the serial parse, and the second pass of Q1 where it applies
+int sim_tables(Sim& s, const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy_lt, uint32_t matching_type, uint32_t* flags) {
     s.n = n;
     s.in.assign(in, in + n);
     s.in.resize(n + 16, 0);
@@ -502,6 +468,46 @@ int hostsim_encode(const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy
         }
         break;
     }
+    return 0;
+}
+
+struct BitSink {
+    std::vector<uint8_t>& out;
+    void put(uint64_t bitpos, uint64_t bits, uint32_t nbits) {
+        for (uint32_t i = 0; i < nbits; i++)
+            if ((bits >> i) & 1) out[(bitpos + i) >> 3] |= (uint8_t)(1u << ((bitpos + i) & 7));
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// encode_lengths_rle (the reference's state machine) against encode_lengths_runs (run by run, what
+// k_block_header does): 0 = same symbols, else 1 + the index of the first difference
+int hostsim_rle_forms_agree(const uint8_t* lens, uint32_t n) {
+    std::vector<uint16_t> a(n + 8), b(n + 8);
+    uint32_t freqs[19] = {0};
+    const uint32_t na = encode_lengths_rle(lens, n, a, freqs);
+    const uint32_t nb = encode_lengths_runs(lens, n, b);
+    if (na != nb) return 1 + (int)std::min(na, nb);
+    for (uint32_t i = 0; i < na; i++)
+        if (a[i] != b[i]) return 1 + (int)i;
+    return 0;
+}
+
+struct hostsim_block {
+    uint32_t btype, bfinal, ntok;
+    uint64_t in_bytes, bit_start;
+};
+
+// returns 0 ok; -3 = reference would panic (Q13 slice out of range); fills *flags with bit0 =
+// Q1 override used, bit1 = Q13 shifted stored source used, bit2 = hierarchical path mismatch
+int hostsim_encode(const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy_lt, uint32_t matching_type,
+                   uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t* flags, hostsim_block* blocks,
+                   uint64_t blocks_cap, uint64_t* n_blocks, uint32_t seg, uint32_t fan) {
+    Sim s;
+    if (const int rc = sim_tables(s, in, n, checks, lazy_lt, matching_type, flags)) return rc;
     if (seg) stage_parse_hier(s, seg, fan ? fan : 4);
     if (s.hier_mismatch) *flags |= 4;
 
@@ -650,6 +656,23 @@ int hostsim_encode(const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy
         if (bp != plan[b].bit_start + plan[b].bit_len) return -5;  // plan/emit disagreement
     }
     memcpy(out, o.data(), total_bytes);
+    return 0;
+}
+
+// the restart steps as k_adv files them (adv_pack of parse_step) for every position, from the tables hostsim_encode uses
+// (after the second pass of Q1 where that applies); nlit_out, if given: the literals in front of the step's match -- the entry's
+// field for them ends at ADV_RUN_MANY
+int hostsim_steps(const uint8_t* in, uint64_t n, uint32_t checks, uint32_t lazy_lt, uint32_t matching_type, uint16_t* steps_out,
+                  uint16_t* nlit_out) {
+    Sim s;
+    uint32_t flags = 0;
+    if (const int rc = sim_tables(s, in, n, checks, lazy_lt, matching_type, &flags)) return rc;
+    MAcc M{s.M.data()}, Mq{s.Mq.data()};
+    for (uint64_t j = 0; j < n; j++) {
+        const Step st = parse_step(M, Mq, j, n, s.cfg);
+        steps_out[j] = (uint16_t)adv_pack(st);
+        if (nlit_out) nlit_out[j] = (uint16_t)st.nlit;
+    }
     return 0;
 }
 

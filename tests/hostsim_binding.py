@@ -27,6 +27,8 @@ def lib():
                                      C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32]
         L.hostsim_encode.restype = C.c_int
         L.hostsim_match_table.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.hostsim_steps.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.hostsim_steps.restype = C.c_int
         L.hostsim_rle_forms_agree.argtypes = [C.c_char_p, C.c_uint32]
         L.hostsim_rle_forms_agree.restype = C.c_int
         _lib = L
@@ -72,6 +74,19 @@ def match_table(data, checks):
     m = (C.c_uint32 * max(n, 1))()
     lib().hostsim_match_table(bytes(data), n, checks, m)
     return list(m[:n])
+
+
+def steps(data, checks, lazy_lt, matching_type, with_nlit=False):
+    """stages.h adv_pack(parse_step(...)) for every position as uint16[n] -- the step's length in bits 0-9, its deferrals (at most
+    ADV_RUN_MANY) in bits 10-14, the quarter table's flag in bit 15 -- from the tables encode() uses, after the second pass of Q1
+    where that applies; with_nlit: and the literals in front of every step's match, uint16[n]"""
+    import numpy as np
+    n = len(data)
+    st = np.zeros(max(n, 1), dtype=np.uint16)
+    nl = np.zeros(max(n, 1), dtype=np.uint16)
+    rc = lib().hostsim_steps(bytes(data), n, checks, lazy_lt, matching_type, st.ctypes.data, nl.ctypes.data if with_nlit else None)
+    assert rc == 0, rc
+    return (st[:n], nl[:n]) if with_nlit else st[:n]
 
 
 def rle_forms_agree(lengths: bytes) -> int:
