@@ -226,6 +226,11 @@ struct mi355_deflate_ctx {
     size_t b_host_cap = 0;
     uint64_t batch_bytes = 256ull << 20;  // MI355_CFG_BATCH_BYTES: input bytes of one launch set
     mi355_batch_info batch = {};          // mi355_deflate_last_batch_info
+    // deflate_verify.inc: the items, entries and records of a verify call (device; page-locked staging)
+    uint8_t* v_dev = nullptr;
+    size_t v_dev_cap = 0;
+    uint8_t* v_host = nullptr;
+    size_t v_host_cap = 0;
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1700,6 +1705,8 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->h_piece) (void)hipHostFree(c->h_piece);
     if (c->b_dev) (void)hipFree(c->b_dev);
     if (c->b_host) (void)hipHostFree(c->b_host);
+    if (c->v_dev) (void)hipFree(c->v_dev);
+    if (c->v_host) (void)hipHostFree(c->v_host);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

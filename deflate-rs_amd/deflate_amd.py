@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MI355_DEFLATE_LIB", os.path.join(_HERE, "libmi355defl
 
 FLUSH_FINISH, FLUSH_SYNC = 0, 1
 OK, E_ARG, E_OUT_TOO_SMALL, E_HIP, E_UNSUPPORTED, E_REF_PANIC, E_STATE = 0, -1, -2, -3, -4, -5, -6
+E_VERIFY = -7
 COMPAT_Q13 = 1
 
 STAGES = ["links", "match", "parse", "blocks", "pack", "other"]
@@ -130,6 +131,22 @@ class BatchInfo(C.Structure):
                 ("sub_batches", C.c_uint32), ("total_ms", C.c_float)]
 
 
+VERIFY_STATUS = ["OK", "FRAME", "BTYPE", "STORED", "LENGTHS", "CODE", "DISTANCE", "MISMATCH", "LENGTH", "TABLE", "TRUNCATED",
+                 "TRAILER", "CHECKSUM"]  # MI355_VERIFY_*
+
+
+class VerifyReport(C.Structure):
+    """mi355_verify_report (48 bytes)"""
+    _fields_ = [("status", C.c_uint32), ("entry", C.c_uint32), ("bit", C.c_uint64), ("in_pos", C.c_uint64),
+                ("n_blocks", C.c_uint64), ("n_stored", C.c_uint32), ("n_fixed", C.c_uint32), ("n_dynamic", C.c_uint32),
+                ("ms", C.c_float)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in VerifyReport._fields_}
+        d["status"] = VERIFY_STATUS[self.status] if self.status < len(VERIFY_STATUS) else self.status
+        return d
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -237,6 +254,12 @@ def load():
     L.mi355_deflate_encode_batch_packed_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.POINTER(Opts),
                                                            C.POINTER(GzipHeader), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                                            C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
+    L.mi355_deflate_verify_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                              C.POINTER(BlockInfo), C.c_size_t, C.POINTER(VerifyReport), C.c_void_p]
+    L.mi355_deflate_verify.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo),
+                                       C.c_size_t, C.POINTER(VerifyReport)]
+    L.mi355_deflate_verify_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.c_int, C.POINTER(VerifyReport),
+                                                    C.c_void_p]
     _lib = L
     return L
 
@@ -262,6 +285,7 @@ EXPORTED = [
     "mi355_deflate_encode_batch", "mi355_deflate_encode_batch_device", "mi355_deflate_last_batch_info",
     "mi355_deflate_encode_batch_gzip", "mi355_deflate_encode_batch_device_gzip",
     "mi355_deflate_batch_packed_bound", "mi355_deflate_encode_batch_packed", "mi355_deflate_encode_batch_packed_device",
+    "mi355_deflate_verify", "mi355_deflate_verify_device", "mi355_deflate_verify_batch_device",
 ]
 
 
@@ -308,8 +332,9 @@ class Context:
         if rc != OK:
             self._err(rc)
 
-    def encode(self, data, options=Compression.Default, wrapper=0, compat=0, flush=0):
-        """Host bytes in, host bytes out (mi355_deflate_encode)."""
+    def encode(self, data, options=Compression.Default, wrapper=0, compat=0, flush=0, verify=False):
+        """Host bytes in, host bytes out (mi355_deflate_encode).  verify: check the stream against the input on the device, with
+        the encode's block table (mi355_deflate_verify), and raise DeflateError(E_VERIFY, ...) if it does not inflate to it."""
         L = load()
         o = CompressionOptions.from_(options).to_c(wrapper, compat, flush)
         data = bytes(data)
@@ -319,7 +344,10 @@ class Context:
         rc = L.mi355_deflate_encode(self._h, data, len(data), C.byref(o), out, cap, C.byref(n))
         if rc != OK:
             self._err(rc)
-        return bytes(memoryview(out)[: n.value])
+        res = bytes(memoryview(out)[: n.value])
+        if verify:
+            self._verify_last(res, data, wrapper)
+        return res
 
     def encode_host_ptr(self, in_ptr, in_len, out_ptr, out_cap, options=Compression.Default, wrapper=0):
         """mi355_deflate_encode on raw host pointers (e.g. pinned buffers): H2D, encode, D2H; returns the length"""
@@ -332,8 +360,8 @@ class Context:
             self._err(rc)
         return n.value
 
-    def encode_gzip(self, data, options=Compression.Default, header=None, compat=0):
-        """mi355_deflate_encode_gzip; header = GzBuilder::into_header() bytes (None: the blank one)."""
+    def encode_gzip(self, data, options=Compression.Default, header=None, compat=0, verify=False):
+        """mi355_deflate_encode_gzip; header = GzBuilder::into_header() bytes (None: the blank one).  verify: as in encode."""
         L = load()
         o = CompressionOptions.from_(options).to_c(2, compat, 0)
         data = bytes(data)
@@ -345,7 +373,10 @@ class Context:
                                          C.byref(n))
         if rc != OK:
             self._err(rc)
-        return bytes(memoryview(out)[: n.value])
+        res = bytes(memoryview(out)[: n.value])
+        if verify:
+            self._verify_last(res, data, 2)
+        return res
 
     def crc32_device(self, d_ptr, n, stream=0):
         a = C.c_uint32(0)
@@ -568,6 +599,74 @@ class Context:
                                                         C.c_void_p(stream))
         return self._packed_result(arena, ap, items, n, used.value, rc, check)
 
+    # ---- verify: does the stream inflate to the input? (mi355_deflate_verify*) ----
+    @staticmethod
+    def _block_table(blocks):
+        """None, a BlockInfo array, or a list of dicts (Context.blocks()) / (bit_start, in_bytes) pairs -> (array or None, n)"""
+        if blocks is None:
+            return None, 0
+        if isinstance(blocks, C.Array):
+            return blocks, len(blocks)
+        arr = (BlockInfo * max(len(blocks), 1))()
+        for k, b in enumerate(blocks):
+            arr[k].bit_start, arr[k].in_bytes = (b["bit_start"], b["in_bytes"]) if isinstance(b, dict) else (b[0], b[1])
+        return arr, len(blocks)
+
+    def verify(self, stream, data, wrapper=0, blocks=None, check=False):
+        """mi355_deflate_verify: host bytes.  blocks: the table of the encode that made the stream (Context.blocks()) or None.
+        Returns (rc, report dict); rc is OK or E_VERIFY.  Other return codes raise, and so does E_VERIFY with check=True."""
+        arr, n = self._block_table(blocks)
+        stream, data = bytes(stream), bytes(data)
+        r = VerifyReport()
+        rc = load().mi355_deflate_verify(self._h, stream, len(stream), data, len(data), wrapper, arr, n, C.byref(r))
+        if rc not in (OK, E_VERIFY) or (rc != OK and check):
+            self._err(rc)
+        return rc, r.as_dict()
+
+    def verify_device(self, d_stream_ptr, stream_len, d_in_ptr, in_len, wrapper=0, blocks=None, stream=0, check=False):
+        """mi355_deflate_verify_device: device pointers; otherwise as verify"""
+        arr, n = self._block_table(blocks)
+        r = VerifyReport()
+        rc = load().mi355_deflate_verify_device(self._h, C.c_void_p(d_stream_ptr), stream_len, C.c_void_p(d_in_ptr), in_len, wrapper,
+                                                arr, n, C.byref(r), C.c_void_p(stream))
+        if rc not in (OK, E_VERIFY) or (rc != OK and check):
+            self._err(rc)
+        return rc, r.as_dict()
+
+    def verify_batch_device(self, items, wrapper=0, stream=0):
+        """mi355_deflate_verify_batch_device.  items: a BatchItem array as a batch encode left it, or a list of
+        (stream pointer, stream length, input pointer, input length) with an optional fifth element, the status on entry.
+        Returns (rc, statuses, report dicts); the statuses of a BatchItem array are also written in place."""
+        if not isinstance(items, C.Array):
+            arr = (BatchItem * max(len(items), 1))()
+            for k, it in enumerate(items):
+                arr[k].out, arr[k].out_len, arr[k].in_, arr[k].in_len = C.c_void_p(it[0]), it[1], C.c_void_p(it[2]), it[3]
+                arr[k].out_cap = it[1]
+                arr[k].status = it[4] if len(it) > 4 else OK
+            n, items = len(items), arr
+        else:
+            n = len(items)
+        reps = (VerifyReport * max(n, 1))()
+        rc = load().mi355_deflate_verify_batch_device(self._h, items, n, wrapper, reps, C.c_void_p(stream))
+        if rc not in (OK, E_VERIFY):
+            self._err(rc)
+        return rc, [items[k].status for k in range(n)], [reps[k].as_dict() for k in range(n)]
+
+    def _verify_last(self, stream, data, wrapper):
+        """the stream of the encode this context has just done against its input, with that encode's block table"""
+        L = load()
+        nb = C.c_size_t(0)
+        L.mi355_deflate_last_blocks(self._h, None, 0, C.byref(nb))
+        arr = (BlockInfo * max(nb.value, 1))()
+        rc = L.mi355_deflate_last_blocks(self._h, arr, nb.value, C.byref(nb))
+        if rc != OK:
+            self._err(rc)
+        r = VerifyReport()
+        rc = L.mi355_deflate_verify(self._h, stream, len(stream), data, len(data), wrapper, arr if nb.value else None, nb.value,
+                                    C.byref(r))
+        if rc != OK:
+            self._err(rc)
+
     def batch_info(self):
         """mi355_deflate_last_batch_info as a dict"""
         i = BatchInfo()
@@ -613,6 +712,12 @@ def default_context():
 
 def bound(n):
     return load().mi355_deflate_bound(n)
+
+
+def verify_bytes(stream, data, wrapper=0, ctx=None):
+    """Does `stream` (raw / zlib / gzip by wrapper) inflate to `data`?  (True, report) or (False, report); on the GPU, no table."""
+    rc, rep = (ctx or default_context()).verify(stream, data, wrapper)
+    return rc == OK, rep
 
 
 # ---- the reference's one-shot functions (src/lib.rs) -------------------------------------------

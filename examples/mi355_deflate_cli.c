@@ -1,7 +1,9 @@
 /* A plain C program over the C ABI of include/mi355_deflate.h (what the Rust shim of INTEGRATION.md
  * binds): compresses a file on the GPU.
- *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] IN OUT
+ *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
+ * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
+ * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
  *             -Wl,-rpath,$PWD/deflate-rs_amd -o /tmp/mi355_deflate_cli */
 #include <stdio.h>
@@ -18,6 +20,7 @@ static int fail(const char* what, int rc, mi355_deflate_ctx* ctx) {
 int main(int argc, char** argv) {
     int wrapper = 0, level = 1;
     size_t chunk = 0;
+    int verify = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "-raw")) wrapper = 0;
@@ -26,11 +29,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[a], "-fast")) level = 0;
         else if (!strcmp(argv[a], "-default")) level = 1;
         else if (!strcmp(argv[a], "-best")) level = 2;
+        else if (!strcmp(argv[a], "--verify") || !strcmp(argv[a], "-verify")) verify = 1;
         else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
     if (argc - a != 2) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] IN OUT\n", argv[0]);
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n", argv[0]);
         return 2;
     }
     FILE* f = fopen(argv[a], "rb");
@@ -68,6 +72,26 @@ int main(int argc, char** argv) {
         rc = mi355_deflate_encode(ctx, in, n, &o, owned, cap, &out_len);
         if (rc) return fail("mi355_deflate_encode", rc, ctx);
         out = owned;
+    }
+    if (verify) { /* with the block table of a one-shot encode: one wave per block; a stream's output: one wave, no table */
+        mi355_block_info* blocks = NULL;
+        size_t n_blocks = 0;
+        mi355_verify_report r;
+        if (!chunk) {
+            if ((rc = mi355_deflate_last_blocks(ctx, NULL, 0, &n_blocks))) return fail("mi355_deflate_last_blocks", rc, ctx);
+            blocks = (mi355_block_info*)malloc((n_blocks ? n_blocks : 1) * sizeof *blocks);
+            if ((rc = mi355_deflate_last_blocks(ctx, blocks, n_blocks, &n_blocks))) return fail("mi355_deflate_last_blocks", rc, ctx);
+        }
+        rc = mi355_deflate_verify(ctx, out, out_len, in, n, wrapper, n_blocks ? blocks : NULL, n_blocks, &r);
+        free(blocks);
+        if (rc != MI355_OK && rc != MI355_E_VERIFY) return fail("mi355_deflate_verify", rc, ctx);
+        fprintf(stderr, "verify: status %u, entry %u, bit %llu, input byte %llu; %llu blocks (%u stored, %u fixed, %u dynamic), %.3f ms\n",
+                r.status, r.entry, (unsigned long long)r.bit, (unsigned long long)r.in_pos, (unsigned long long)r.n_blocks, r.n_stored,
+                r.n_fixed, r.n_dynamic, r.ms);
+        if (rc == MI355_E_VERIFY) {
+            fprintf(stderr, "%s\n", mi355_deflate_last_error(ctx));
+            return 3;
+        }
     }
     f = fopen(argv[a + 1], "wb");
     if (!f || fwrite(out, 1, out_len, f) != out_len) return fail("write output", -1, NULL);

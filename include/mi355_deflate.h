@@ -35,6 +35,7 @@ extern "C" {
 #define MI355_E_REF_PANIC (-5)     /* the reference itself panics on this input (A.4 Q13, slice out
                                       of range) and MI355_COMPAT_Q13 was requested */
 #define MI355_E_STATE (-6)         /* stream used after finish, or after a range of it failed; context busy with a shard */
+#define MI355_E_VERIFY (-7)        /* the stream is not a valid raw / zlib / gzip deflate stream of this input; see the report */
 
 /* CompressionOptions (src/compression_options.rs:78-120) + MatchingType (src/lz77.rs:27-37).
  * `special` has only the Normal variant reachable from the public API and is omitted. */
@@ -357,6 +358,70 @@ int mi355_deflate_encode_batch_packed_device(mi355_deflate_ctx* ctx, mi355_batch
                                              const mi355_deflate_opts* opts, const mi355_gzip_header* hdrs, size_t n_hdrs,
                                              void* d_arena, size_t arena_cap, size_t align, mi355_packed_entry* d_table,
                                              size_t* arena_used, void* hip_stream);
+
+/* ---- verify: does this stream inflate to this input? ------------------------------------------------
+ * What `gzip -t` and `zstd --check` answer, on the device and without writing a byte: the expected output is the input, so a
+ * literal is right when it equals in[p] and a match (len, dist) at p when in[p + i] == in[p + i - dist] for i < len.  No reference
+ * item: the reference has no decoder.  FINISH streams only (the last block carries BFINAL); pad bits behind the BFINAL block and
+ * in front of a stored LEN are ignored, as zlib's inflate does; in_len at most 4 GiB - 64 KiB (more: MI355_E_UNSUPPORTED), 0 is legal.
+ * blocks / n_blocks (host memory): what mi355_deflate_last_blocks returned for the encode that made the stream; only bit_start and
+ *   in_bytes are read.  The table is a set of restart points, checked by one wave each: entry e starts at bit bit_start[e] of the
+ *   raw stream and its first output byte is in[sum of in_bytes[k], k < e].  An entry may hold several deflate blocks (an encoder
+ *   "stored block" is a run of stored pieces; empty blocks are legal): after each one a non-last entry is done when it stands
+ *   exactly at the next entry's bit and input offset, and passing either is MI355_VERIFY_TABLE.  blocks == NULL: one entry at
+ *   (0, 0) -- one wave walks the whole stream: for small streams and for streams made elsewhere.  bit_start values that do not
+ *   ascend, or in_bytes that do not sum to in_len, are MI355_E_ARG.
+ * wrapper: as in mi355_deflate_opts.  1: CM = 8, CINFO <= 7, FCHECK, no FDICT, Adler-32 big endian behind the data.  2: the RFC 1952
+ *   header (ID1, ID2, CM, reserved FLG bits clear; FEXTRA, FNAME, FCOMMENT and FHCRC are skipped; it must end within 64 KiB + 32
+ *   bytes), then CRC-32 and ISIZE little endian.  Anything else is MI355_E_ARG.
+ * Returns MI355_OK when the stream verifies and MI355_E_VERIFY when it does not; the report is filled either way and
+ *   mi355_deflate_last_error gives one line.  FRAME is reported first, then the failing entry with the smallest index and inside it
+ *   the first failure in stream order; TRAILER / CHECKSUM only when every entry is clean.  The result is a function of the
+ *   arguments alone.  MI355_E_ARG, MI355_E_HIP and MI355_E_STATE (live shard) as elsewhere.  A verify call does not disturb
+ *   mi355_deflate_last_info / _last_blocks / _last_batch_info of the encode before it.
+ * A dynamic header is judged by zlib's rules (MI355_VERIFY_LENGTHS): more than 286 literal/length or 30 distance codes; a
+ *   code-length code that is not complete; repeat code 16 with nothing before it; a repeat that runs past HLIT + HDIST; no code
+ *   for symbol 256; a set that is over-subscribed, or incomplete unless it is exactly one code of length 1.  All distance lengths
+ *   zero is legal (a length symbol then fails as MI355_VERIFY_CODE).
+ * _device: d_stream / d_in are device pointers of any alignment; hip_stream NULL = the context's stream; the call returns after the
+ *   stream has drained.  Without _device they are host pointers, copied into the context's staging buffers.
+ * _batch_device: item i is verified without a table -- in / in_len is the input, out / out_len the stream, as a batch encode left
+ *   them (the packed entries' out pointers into the arena work too).  Items whose status on entry is not MI355_OK are skipped and
+ *   left alone; for the others status becomes MI355_OK or MI355_E_VERIFY and reports[i] (if reports is not NULL) is filled.  The
+ *   call returns the first failing item's status.  One launch for all items, one workgroup per item. */
+#define MI355_VERIFY_OK        0
+#define MI355_VERIFY_FRAME     1  /* zlib / gzip header malformed, or the stream is shorter than its frame */
+#define MI355_VERIFY_BTYPE     2  /* BTYPE 3 */
+#define MI355_VERIFY_STORED    3  /* LEN != ~NLEN */
+#define MI355_VERIFY_LENGTHS   4  /* dynamic header: see the rules above */
+#define MI355_VERIFY_CODE      5  /* bits that are no code of the set; ll symbol 286/287; distance symbol 30/31 */
+#define MI355_VERIFY_DISTANCE  6  /* distance > 32768 or > the bytes produced so far (counted from input position 0) */
+#define MI355_VERIFY_MISMATCH  7  /* a literal, a match or a stored byte differs from the input */
+#define MI355_VERIFY_LENGTH    8  /* last entry / no table: a token runs past in_len, or the BFINAL block ends before in_len */
+#define MI355_VERIFY_TABLE     9  /* with a table: an entry's blocks do not end exactly at the next entry's bit_start and input
+                                     offset, or BFINAL is met before the last entry */
+#define MI355_VERIFY_TRUNCATED 10 /* bits needed beyond the end of the deflate data (incl. no BFINAL block before it) */
+#define MI355_VERIFY_TRAILER   11 /* bytes between the end of the BFINAL block and the trailer, or after it */
+#define MI355_VERIFY_CHECKSUM  12 /* Adler-32 (zlib) / CRC-32 or ISIZE (gzip) in the trailer is not the input's */
+
+typedef struct {
+    uint32_t status;    /* MI355_VERIFY_* */
+    uint32_t entry;     /* index into blocks[] of the failing entry (0 without a table) */
+    uint64_t bit;       /* raw-deflate bit offset (frame header excluded) where the failing element begins:
+                           the block header, the code-length section, the code, the LEN field */
+    uint64_t in_pos;    /* MISMATCH: the first input byte that differs; else the bytes produced before the element */
+    uint64_t n_blocks;  /* OK only: deflate blocks decoded (a stored piece counts as one) */
+    uint32_t n_stored, n_fixed, n_dynamic;
+    float ms;           /* host clock over the call */
+} mi355_verify_report;  /* 48 bytes */
+
+int mi355_deflate_verify_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, const void* d_in, size_t in_len,
+                                int wrapper, const mi355_block_info* blocks, size_t n_blocks, mi355_verify_report* report,
+                                void* hip_stream);
+int mi355_deflate_verify(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, const uint8_t* in, size_t in_len,
+                         int wrapper, const mi355_block_info* blocks, size_t n_blocks, mi355_verify_report* report);
+int mi355_deflate_verify_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items, int wrapper,
+                                      mi355_verify_report* reports /* n_items entries, or NULL */, void* hip_stream);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
