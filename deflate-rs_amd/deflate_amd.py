@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MI355_DEFLATE_LIB", os.path.join(_HERE, "libmi355defl
 FLUSH_FINISH, FLUSH_SYNC = 0, 1
 OK, E_ARG, E_OUT_TOO_SMALL, E_HIP, E_UNSUPPORTED, E_REF_PANIC, E_STATE = 0, -1, -2, -3, -4, -5, -6
 E_VERIFY = -7
+E_DATA = -8
 COMPAT_Q13 = 1
 
 STAGES = ["links", "match", "parse", "blocks", "pack", "other"]
@@ -147,6 +148,18 @@ class VerifyReport(C.Structure):
         return d
 
 
+class InflateReport(C.Structure):
+    """mi355_inflate_report (56 bytes)"""
+    _fields_ = [("status", C.c_uint32), ("reserved", C.c_uint32), ("bit", C.c_uint64), ("out_pos", C.c_uint64),
+                ("out_len", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored", C.c_uint32), ("n_fixed", C.c_uint32),
+                ("n_dynamic", C.c_uint32), ("ms", C.c_float)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in InflateReport._fields_ if k != "reserved"}
+        d["status"] = VERIFY_STATUS[self.status] if self.status < len(VERIFY_STATUS) else self.status
+        return d
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -260,6 +273,12 @@ def load():
                                        C.c_size_t, C.POINTER(VerifyReport)]
     L.mi355_deflate_verify_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.c_int, C.POINTER(VerifyReport),
                                                     C.c_void_p]
+    L.mi355_inflate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                       C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                C.POINTER(InflateReport)]
+    L.mi355_inflate_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.c_int, C.POINTER(InflateReport),
+                                             C.c_void_p]
     _lib = L
     return L
 
@@ -286,6 +305,7 @@ EXPORTED = [
     "mi355_deflate_encode_batch_gzip", "mi355_deflate_encode_batch_device_gzip",
     "mi355_deflate_batch_packed_bound", "mi355_deflate_encode_batch_packed", "mi355_deflate_encode_batch_packed_device",
     "mi355_deflate_verify", "mi355_deflate_verify_device", "mi355_deflate_verify_batch_device",
+    "mi355_inflate", "mi355_inflate_device", "mi355_inflate_batch_device",
 ]
 
 
@@ -667,6 +687,66 @@ class Context:
         if rc != OK:
             self._err(rc)
 
+    # ---- inflate: the stream's bytes (mi355_inflate*) ----
+    def inflate_raw(self, stream, wrapper=0, out_cap=0):
+        """mi355_inflate on host bytes, nothing raised for the three outcomes of a decode: (rc, out_len, report dict, the bytes
+        of the buffer that hold data).  rc is OK, E_DATA or E_OUT_TOO_SMALL; out_cap 0 hands over no buffer (the size query)."""
+        stream = bytes(stream)
+        out = (C.c_uint8 * out_cap)() if out_cap else None
+        n = C.c_size_t(0)
+        r = InflateReport()
+        rc = load().mi355_inflate(self._h, stream, len(stream), wrapper, C.cast(out, C.c_void_p) if out_cap else None, out_cap,
+                                  C.byref(n), C.byref(r))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL):
+            self._err(rc)
+        held = min(n.value, out_cap)
+        return rc, n.value, r.as_dict(), bytes(memoryview(out)[:held]) if held else b""
+
+    def inflate(self, stream, wrapper=0, out_cap=None):
+        """Host bytes in, the bytes the stream (raw / zlib / gzip by wrapper) inflates to out.  out_cap None: the size is queried
+        first (one decode that stores nothing), then the stream is decoded.  Raises DeflateError(E_DATA, ...) for a stream that
+        is not valid and DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap."""
+        if out_cap is None:
+            rc, out_cap, _rep, _ = self.inflate_raw(stream, wrapper, 0)
+            if rc == E_DATA:
+                self._err(rc)
+        rc, _n, _rep, data = self.inflate_raw(stream, wrapper, out_cap)
+        if rc != OK:
+            self._err(rc)
+        return data
+
+    def inflate_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, wrapper=0, stream=0, check=False):
+        """mi355_inflate_device: device pointers.  Returns (rc, out_len, report dict); rc is OK, E_DATA or E_OUT_TOO_SMALL.
+        Other return codes raise, and so do those two with check=True."""
+        n = C.c_size_t(0)
+        r = InflateReport()
+        rc = load().mi355_inflate_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, C.c_void_p(d_out_ptr), out_cap,
+                                         C.byref(n), C.byref(r), C.c_void_p(stream))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL) or (rc != OK and check):
+            self._err(rc)
+        return rc, n.value, r.as_dict()
+
+    def inflate_batch_device(self, items, wrapper=0, stream=0):
+        """mi355_inflate_batch_device.  items: a BatchItem array (in_ / in_len the stream, out / out_cap the buffer, e.g. the out
+        pointers of a packed arena moved to in_), or a list of (stream pointer, stream length, buffer pointer, buffer size) with an
+        optional fifth element, the status on entry.  Returns (rc, report dicts); out_len and status are written into the array,
+        which is the second element's `items` attribute when a list was given."""
+        if not isinstance(items, C.Array):
+            arr = (BatchItem * max(len(items), 1))()
+            for k, it in enumerate(items):
+                arr[k].in_, arr[k].in_len, arr[k].out, arr[k].out_cap = C.c_void_p(it[0]), it[1], C.c_void_p(it[2]), it[3]
+                arr[k].status = it[4] if len(it) > 4 else OK
+            n, items = len(items), arr
+        else:
+            n = len(items)
+        reps = (InflateReport * max(n, 1))()
+        rc = load().mi355_inflate_batch_device(self._h, items, n, wrapper, reps, C.c_void_p(stream))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL):
+            self._err(rc)
+        out = InflateReports(reps[k].as_dict() for k in range(n))
+        out.items = items
+        return rc, out
+
     def batch_info(self):
         """mi355_deflate_last_batch_info as a dict"""
         i = BatchInfo()
@@ -712,6 +792,16 @@ def default_context():
 
 def bound(n):
     return load().mi355_deflate_bound(n)
+
+
+class InflateReports(list):
+    """the report dicts of an inflate batch; .items is the BatchItem array the call wrote out_len and status into"""
+    items = None
+
+
+def inflate_bytes(stream, wrapper=0, ctx=None):
+    """The bytes `stream` (raw / zlib / gzip by wrapper) inflates to, decoded on the GPU; DeflateError(E_DATA, ...) if it is not valid."""
+    return (ctx or default_context()).inflate(stream, wrapper)
 
 
 def verify_bytes(stream, data, wrapper=0, ctx=None):

@@ -36,6 +36,7 @@ extern "C" {
                                       of range) and MI355_COMPAT_Q13 was requested */
 #define MI355_E_STATE (-6)         /* stream used after finish, or after a range of it failed; context busy with a shard */
 #define MI355_E_VERIFY (-7)        /* the stream is not a valid raw / zlib / gzip deflate stream of this input; see the report */
+#define MI355_E_DATA (-8)          /* inflate: the stream is not a valid raw / zlib / gzip deflate stream; see the report */
 
 /* CompressionOptions (src/compression_options.rs:78-120) + MatchingType (src/lz77.rs:27-37).
  * `special` has only the Normal variant reachable from the public API and is omitted. */
@@ -422,6 +423,55 @@ int mi355_deflate_verify(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t s
                          int wrapper, const mi355_block_info* blocks, size_t n_blocks, mi355_verify_report* report);
 int mi355_deflate_verify_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items, int wrapper,
                                       mi355_verify_report* reports /* n_items entries, or NULL */, void* hip_stream);
+
+/* ---- inflate: decode one stream, or a batch of streams, to its bytes on the device -----------------------
+ * The other half of the batch entry points: what the library wrote into device memory -- one stream, the items of a batch, the
+ * regions of a packed arena -- is decoded where it lies.  No reference item: the reference has no decoder.  Streams made by anyone
+ * are accepted, not only ones this library encoded; pointers of any alignment.
+ * wrapper: 0 / 1 / 2 as in verify, and the framing rules are verify's: zlib with FDICT is MI355_VERIFY_FRAME; ONE gzip member
+ *   only, bytes after the trailer are MI355_VERIFY_TRAILER (so are bytes behind the BFINAL block of a raw stream); pad bits
+ *   are ignored, as zlib does; a dynamic header is judged by zlib's rules (see verify).  Anything else is MI355_E_ARG.
+ * Return value, for one stream and for each item of a batch:
+ *   MI355_OK               out[0, out_len) is the data; report.out_pos == report.out_len.
+ *   MI355_E_DATA           the report names the first failure in stream order (status, bit, out_pos); out[0, min(out_pos, out_cap))
+ *                          holds the bytes decoded in front of it -- literals gathered in front of the failing element are written
+ *                          before it is reported -- and nothing is written at or beyond out_pos.  *out_len = the bytes that hold data.
+ *   MI355_E_OUT_TOO_SMALL  the stream is structurally valid but longer than out_cap: the decode went on COUNTING without storing, so
+ *                          *out_len / report.out_len is the exact size needed and out[0, out_cap) holds the first out_cap bytes.  The
+ *                          checksum is not judged.  out_cap == 0 with out == NULL is a legal size query.
+ *   No store ever lands at an index >= out_cap, and no load of the output happens at an index >= min(p, out_cap), p being the
+ *   bytes produced so far.  A framed stream that inflates to more than 4 GiB - 64 KiB is MI355_E_UNSUPPORTED (the checksum kernels).
+ * ctx == NULL (the default context), a live shard (MI355_E_STATE), MI355_E_ARG and MI355_E_HIP: as in verify.  _device: device
+ *   pointers; hip_stream NULL = the context's stream; the call returns after the stream has drained.  Without _device they are host
+ *   pointers: the stream is copied into the context's staging and the bytes that hold data are copied back.  An inflate call leaves
+ *   mi355_deflate_last_info / _last_blocks / _last_batch_info alone; mi355_deflate_last_error gives one line.
+ * Checksums (wrapper 1 / 2): the output's length exists only after the decode, so a framed call waits twice: the decode and its
+ *   records, then the encode's checksum kernels over the outputs that are structurally valid and fit, and a small kernel that
+ *   compares them (and ISIZE) with the trailers: MI355_VERIFY_CHECKSUM.  A raw call waits once.
+ * _batch_device: the direction is the natural one for a decoder and the REVERSE of mi355_deflate_verify_batch_device: in / in_len
+ *   is the stream (the out pointers of a packed arena's items go here), out / out_cap the buffer; out_len and status are written,
+ *   and reports[i] if reports is not NULL.  Items whose status on entry is not MI355_OK are skipped and left alone.  A failing item
+ *   disturbs no neighbour; the call returns the first failing item's status.  One decode launch for all items, one workgroup per item.
+ * Speed: ONE wave walks a whole stream, symbol after symbol, so a large single stream is slow; the entry points are
+ *   made for many streams at once -- pages, tiles, the items of a batch. */
+typedef struct {
+    uint32_t status;    /* MI355_VERIFY_OK, _FRAME, _BTYPE, _STORED, _LENGTHS, _CODE, _DISTANCE, _TRUNCATED, _TRAILER, _CHECKSUM
+                           (never _MISMATCH, _LENGTH, _TABLE: there is no input and no table) */
+    uint32_t reserved;  /* 0 */
+    uint64_t bit;       /* raw-deflate bit offset where the failing element begins (verify's rule) */
+    uint64_t out_pos;   /* bytes produced before the failing element; == out_len when OK */
+    uint64_t out_len;   /* bytes the stream inflates to (OK, and OUT_TOO_SMALL: the exact size needed); 0 after a failure */
+    uint64_t n_blocks;  /* not after a failure: deflate blocks decoded (a stored piece counts as one) */
+    uint32_t n_stored, n_fixed, n_dynamic;
+    float ms;           /* host clock over the call */
+} mi355_inflate_report; /* 56 bytes */
+
+int mi355_inflate_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, int wrapper, void* d_out, size_t out_cap,
+                         size_t* out_len, mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, int wrapper, uint8_t* out, size_t out_cap,
+                  size_t* out_len, mi355_inflate_report* report);
+int mi355_inflate_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items, int wrapper,
+                               mi355_inflate_report* reports /* n_items entries, or NULL */, void* hip_stream);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
