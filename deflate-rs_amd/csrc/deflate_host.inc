@@ -231,6 +231,13 @@ struct mi355_deflate_ctx {
     size_t v_dev_cap = 0;
     uint8_t* v_host = nullptr;
     size_t v_host_cap = 0;
+    // deflate_table_inflate.inc: the symbols and the resolved windows of a group of entries
+    uint8_t* t_dev = nullptr;
+    size_t t_dev_cap = 0;
+    uint64_t inflate_group_bytes = 256ull << 20;  // MI355_CFG_INFLATE_GROUP_BYTES: output bytes of one group of entries
+    hipEvent_t t_ev[4] = {};                      // between the launch kinds of a tabled inflate, when the stage clocks are on
+    bool t_ev_ok = false;
+    float t_ms[4] = {};                           // mi355_inflate_tabled_last_stages: decode, windows, resolve, checksums
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1707,6 +1714,9 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->b_host) (void)hipHostFree(c->b_host);
     if (c->v_dev) (void)hipFree(c->v_dev);
     if (c->v_host) (void)hipHostFree(c->v_host);
+    if (c->t_dev) (void)hipFree(c->t_dev);
+    if (c->t_ev_ok)
+        for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->t_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

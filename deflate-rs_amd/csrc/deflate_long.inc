@@ -629,6 +629,10 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
         if (value < (1ull << 20) || value > (1ull << 30)) return MI355_E_ARG;
         c->batch_bytes = value;
         return MI355_OK;
+    case MI355_CFG_INFLATE_GROUP_BYTES:
+        if (value < (64ull << 10)) return MI355_E_ARG;
+        c->inflate_group_bytes = value;
+        return MI355_OK;
     case MI355_CFG_SORT_RANKS:
         if (value > 1) return MI355_E_ARG;
         if (value == 1 && !c->lds_order_ok) return MI355_E_UNSUPPORTED;  // the device failed the self-test

@@ -279,6 +279,11 @@ def load():
                                 C.POINTER(InflateReport)]
     L.mi355_inflate_batch_device.argtypes = [C.c_void_p, C.POINTER(BatchItem), C.c_size_t, C.c_int, C.POINTER(InflateReport),
                                              C.c_void_p]
+    L.mi355_inflate_tabled_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t, C.c_void_p,
+                                              C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_tabled.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t, C.c_void_p,
+                                       C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport)]
+    L.mi355_inflate_tabled_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -306,6 +311,7 @@ EXPORTED = [
     "mi355_deflate_batch_packed_bound", "mi355_deflate_encode_batch_packed", "mi355_deflate_encode_batch_packed_device",
     "mi355_deflate_verify", "mi355_deflate_verify_device", "mi355_deflate_verify_batch_device",
     "mi355_inflate", "mi355_inflate_device", "mi355_inflate_batch_device",
+    "mi355_inflate_tabled", "mi355_inflate_tabled_device", "mi355_inflate_tabled_last_stages",
 ]
 
 
@@ -338,6 +344,7 @@ class Context:
 
     CFG_RANGE_BYTES, CFG_LONG_FROM, CFG_SORT_RANKS, CFG_HOST_STREAMING, CFG_MULTI_STITCH, CFG_STEPS_IN_EMIT = 1, 2, 3, 4, 5, 6
     CFG_HOST_BOUNCE, CFG_HOST_THREADS, CFG_STAGE_CLOCKS, CFG_BATCH_BYTES = 7, 8, 9, 10
+    CFG_INFLATE_GROUP_BYTES = 11
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -688,43 +695,63 @@ class Context:
             self._err(rc)
 
     # ---- inflate: the stream's bytes (mi355_inflate*) ----
-    def inflate_raw(self, stream, wrapper=0, out_cap=0):
+    def inflate_raw(self, stream, wrapper=0, out_cap=0, blocks=None):
         """mi355_inflate on host bytes, nothing raised for the three outcomes of a decode: (rc, out_len, report dict, the bytes
-        of the buffer that hold data).  rc is OK, E_DATA or E_OUT_TOO_SMALL; out_cap 0 hands over no buffer (the size query)."""
+        of the buffer that hold data).  rc is OK, E_DATA or E_OUT_TOO_SMALL; out_cap 0 hands over no buffer (the size query).
+        blocks: the table of the encode that made the stream (Context.blocks()): mi355_inflate_tabled, every entry decoded on its own."""
         stream = bytes(stream)
         out = (C.c_uint8 * out_cap)() if out_cap else None
         n = C.c_size_t(0)
         r = InflateReport()
-        rc = load().mi355_inflate(self._h, stream, len(stream), wrapper, C.cast(out, C.c_void_p) if out_cap else None, out_cap,
-                                  C.byref(n), C.byref(r))
+        if blocks is None:
+            rc = load().mi355_inflate(self._h, stream, len(stream), wrapper, C.cast(out, C.c_void_p) if out_cap else None, out_cap,
+                                      C.byref(n), C.byref(r))
+        else:
+            arr, nb = self._block_table(blocks)
+            rc = load().mi355_inflate_tabled(self._h, stream, len(stream), wrapper, arr, nb, C.cast(out, C.c_void_p) if out_cap else None,
+                                             out_cap, C.byref(n), C.byref(r))
         if rc not in (OK, E_DATA, E_OUT_TOO_SMALL):
             self._err(rc)
         held = min(n.value, out_cap)
         return rc, n.value, r.as_dict(), bytes(memoryview(out)[:held]) if held else b""
 
-    def inflate(self, stream, wrapper=0, out_cap=None):
+    def inflate(self, stream, wrapper=0, out_cap=None, blocks=None):
         """Host bytes in, the bytes the stream (raw / zlib / gzip by wrapper) inflates to out.  out_cap None: the size is queried
         first (one decode that stores nothing), then the stream is decoded.  Raises DeflateError(E_DATA, ...) for a stream that
-        is not valid and DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap."""
+        is not valid and DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap.  blocks: as in inflate_raw."""
         if out_cap is None:
-            rc, out_cap, _rep, _ = self.inflate_raw(stream, wrapper, 0)
+            rc, out_cap, _rep, _ = self.inflate_raw(stream, wrapper, 0, blocks)
             if rc == E_DATA:
                 self._err(rc)
-        rc, _n, _rep, data = self.inflate_raw(stream, wrapper, out_cap)
+        rc, _n, _rep, data = self.inflate_raw(stream, wrapper, out_cap, blocks)
         if rc != OK:
             self._err(rc)
         return data
 
-    def inflate_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, wrapper=0, stream=0, check=False):
+    def inflate_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, wrapper=0, stream=0, check=False, blocks=None):
         """mi355_inflate_device: device pointers.  Returns (rc, out_len, report dict); rc is OK, E_DATA or E_OUT_TOO_SMALL.
-        Other return codes raise, and so do those two with check=True."""
+        Other return codes raise, and so do those two with check=True.  blocks: the table of the encode that made the stream
+        (Context.blocks()): mi355_inflate_tabled_device."""
         n = C.c_size_t(0)
         r = InflateReport()
-        rc = load().mi355_inflate_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, C.c_void_p(d_out_ptr), out_cap,
-                                         C.byref(n), C.byref(r), C.c_void_p(stream))
+        if blocks is None:
+            rc = load().mi355_inflate_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, C.c_void_p(d_out_ptr), out_cap,
+                                             C.byref(n), C.byref(r), C.c_void_p(stream))
+        else:
+            arr, nb = self._block_table(blocks)
+            rc = load().mi355_inflate_tabled_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, arr, nb, C.c_void_p(d_out_ptr),
+                                                    out_cap, C.byref(n), C.byref(r), C.c_void_p(stream))
         if rc not in (OK, E_DATA, E_OUT_TOO_SMALL) or (rc != OK and check):
             self._err(rc)
         return rc, n.value, r.as_dict()
+
+    def inflate_tabled_stages(self):
+        """mi355_inflate_tabled_last_stages: HIP-event ms of the last tabled inflate per launch kind (zeros without CFG_STAGE_CLOCKS)"""
+        ms = (C.c_float * 4)()
+        rc = load().mi355_inflate_tabled_last_stages(self._h, ms)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("decode_ms", "windows_ms", "resolve_ms", "checksums_ms"), ms))
 
     def inflate_batch_device(self, items, wrapper=0, stream=0):
         """mi355_inflate_batch_device.  items: a BatchItem array (in_ / in_len the stream, out / out_cap the buffer, e.g. the out
@@ -799,9 +826,10 @@ class InflateReports(list):
     items = None
 
 
-def inflate_bytes(stream, wrapper=0, ctx=None):
-    """The bytes `stream` (raw / zlib / gzip by wrapper) inflates to, decoded on the GPU; DeflateError(E_DATA, ...) if it is not valid."""
-    return (ctx or default_context()).inflate(stream, wrapper)
+def inflate_bytes(stream, wrapper=0, ctx=None, blocks=None):
+    """The bytes `stream` (raw / zlib / gzip by wrapper) inflates to, decoded on the GPU; DeflateError(E_DATA, ...) if it is not valid.
+    blocks: the block table of the encode that made the stream, for a parallel decode (Context.inflate)."""
+    return (ctx or default_context()).inflate(stream, wrapper, blocks=blocks)
 
 
 def verify_bytes(stream, data, wrapper=0, ctx=None):

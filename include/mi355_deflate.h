@@ -156,7 +156,11 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *                          and total_ms is the host's clock from the call's first launch to the return of its last wait.
  *                          (The environment variable MI355_STAGE_CLOCKS sets the default: a measuring aid.)
  *   MI355_CFG_BATCH_BYTES  input bytes of one launch set of mi355_deflate_encode_batch[_device] (default 256 MiB; 1 MiB .. 1 GiB):
- *                          a batch with more is cut into consecutive sub-batches.  Same bytes either way. */
+ *                          a batch with more is cut into consecutive sub-batches.  Same bytes either way.
+ *   MI355_CFG_INFLATE_GROUP_BYTES  output bytes of one group of table entries of mi355_inflate_tabled[_device] (default 256 MiB;
+ *                          at least 64 KiB): a group's workspace is two bytes per output byte plus 32 KiB per entry, so a longer
+ *                          stream is decoded group after group.  An entry larger than this is a group of its own.  Same bytes
+ *                          either way. */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -167,6 +171,7 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_HOST_THREADS 8
 #define MI355_CFG_STAGE_CLOCKS 9
 #define MI355_CFG_BATCH_BYTES 10
+#define MI355_CFG_INFLATE_GROUP_BYTES 11
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
@@ -453,10 +458,11 @@ int mi355_deflate_verify_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* 
  *   and reports[i] if reports is not NULL.  Items whose status on entry is not MI355_OK are skipped and left alone.  A failing item
  *   disturbs no neighbour; the call returns the first failing item's status.  One decode launch for all items, one workgroup per item.
  * Speed: ONE wave walks a whole stream, symbol after symbol, so a large single stream is slow; the entry points are
- *   made for many streams at once -- pages, tiles, the items of a batch. */
+ *   made for many streams at once -- pages, tiles, the items of a batch.  For one large stream whose block table was kept:
+ *   mi355_inflate_tabled[_device] below. */
 typedef struct {
     uint32_t status;    /* MI355_VERIFY_OK, _FRAME, _BTYPE, _STORED, _LENGTHS, _CODE, _DISTANCE, _TRUNCATED, _TRAILER, _CHECKSUM
-                           (never _MISMATCH, _LENGTH, _TABLE: there is no input and no table) */
+                           (never _MISMATCH, _LENGTH: there is no input), and _TABLE from mi355_inflate_tabled* */
     uint32_t reserved;  /* 0 */
     uint64_t bit;       /* raw-deflate bit offset where the failing element begins (verify's rule) */
     uint64_t out_pos;   /* bytes produced before the failing element; == out_len when OK */
@@ -472,6 +478,39 @@ int mi355_inflate(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_l
                   size_t* out_len, mi355_inflate_report* report);
 int mi355_inflate_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* items, size_t n_items, int wrapper,
                                mi355_inflate_report* reports /* n_items entries, or NULL */, void* hip_stream);
+
+/* ---- tabled inflate: ONE large stream decoded in parallel from its encoder block table ---------------------
+ * The way back for a stream this library encoded and whose block table the caller kept (mi355_deflate_last_blocks): entry e of the
+ * table starts at bit bit_start[e] and at output position sum of in_bytes[k], k < e, so every entry is decoded by a wave of its own
+ * -- into 16-bit symbols, a byte or "byte j of the 32 KiB in front of this entry" --, one workgroup then makes the resolved 32 KiB
+ * window behind every entry, one entry after the other, and a flat launch turns symbols into bytes.  Nothing waits inside a kernel.
+ * The contract is mi355_inflate[_device]'s: wrappers and framing rules, MI355_OK / MI355_E_DATA / MI355_E_OUT_TOO_SMALL with the
+ *   exact size (the table's sum, once every entry has been found to end where the next begins), the size query, out[0, min(out_pos,
+ *   out_cap)) = the data decoded in front of the first failure and nothing at or beyond it, the trailer's checksum judged over the
+ *   output, MI355_E_STATE / _ARG / _HIP / _UNSUPPORTED as there.
+ * The table's rules are verify's: only bit_start and in_bytes are read; blocks in HOST memory; bit_start values that do not ascend
+ *   are MI355_E_ARG, and so is a first entry that does not begin at bit 0 (like every argument error of a tabled call, decided
+ *   before a context or the device is touched; mi355_deflate_last_error of the context given has the reason); n_blocks == 0 or
+ *   blocks == NULL means no table and the call IS mi355_inflate[_device].
+ * MI355_VERIFY_TABLE is a status a tabled inflate reports: an entry's last block does not end exactly at the next entry's bit and
+ *   output position, a token would pass that position, BFINAL before the last entry, or the BFINAL block ends at a position other
+ *   than the sum of in_bytes.  Because entry 0 must begin at bit 0 and every entry must end exactly where the next begins, a table
+ *   that passes describes the one serial walk of the stream: a wrong table never yields wrong bytes with MI355_OK.  The report is the first failing entry's in
+ *   stream order; on success the block counts are the sums over the entries.
+ * Entries are worked on in groups of consecutive entries -- MI355_CFG_INFLATE_GROUP_BYTES output bytes or 4096 entries, whichever
+ *   comes first -- with a workspace of two bytes per output byte of the group plus 32 KiB per entry; one wait per group, and one
+ *   more for the checksum of a framed stream. */
+int mi355_inflate_tabled_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, int wrapper,
+                                const mi355_block_info* blocks, size_t n_blocks, void* d_out, size_t out_cap, size_t* out_len,
+                                mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_tabled(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, int wrapper,
+                         const mi355_block_info* blocks, size_t n_blocks, uint8_t* out, size_t out_cap, size_t* out_len,
+                         mi355_inflate_report* report);
+/* Diagnostics, for tools/inflate_table_bench.py -- a measuring aid, not part of the stable interface, and it may change with the
+ * kernels it times: HIP-event milliseconds of the context's last tabled call per launch kind, summed over its groups -- ms[0] the decode
+ * (a wave per entry), ms[1] the window chain, ms[2] the resolve, ms[3] the checksum half of a framed call.  Zeros unless the stage
+ * clocks were on for the call (MI355_CFG_STAGE_CLOCKS = 1, or 2 for tables of 32 MiB or more). */
+int mi355_inflate_tabled_last_stages(mi355_deflate_ctx* ctx, float ms[4]);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
