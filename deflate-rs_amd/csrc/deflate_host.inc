@@ -238,6 +238,12 @@ struct mi355_deflate_ctx {
     hipEvent_t t_ev[4] = {};                      // between the launch kinds of a tabled inflate, when the stage clocks are on
     bool t_ev_ok = false;
     float t_ms[4] = {};                           // mi355_inflate_tabled_last_stages: decode, windows, resolve, checksums
+    // deflate_index_inflate.inc: the block table of a stream nobody kept one for
+    uint64_t index_span = 16384;  // MI355_CFG_INFLATE_INDEX_SPAN_BYTES: compressed bytes of one span (ix::SPAN_DEFAULT)
+    hipEvent_t x_ev[3] = {};      // around the two launches of an index, when the stage clocks are on
+    bool x_ev_ok = false;
+    float x_ms[3] = {};           // mi355_inflate_index_last_stages: find, walk, host link
+    std::vector<uint8_t> x_walks; // mi355_inflate_index_last_walks: the last index's records, 80 bytes a span
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1717,6 +1723,8 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->t_dev) (void)hipFree(c->t_dev);
     if (c->t_ev_ok)
         for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->t_ev[k]);
+    if (c->x_ev_ok)
+        for (int k = 0; k < 3; k++) (void)hipEventDestroy(c->x_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

@@ -160,6 +160,14 @@ class InflateReport(C.Structure):
         return d
 
 
+class IndexWalk(C.Structure):
+    """mi355_index_walk (80 bytes): what the walker of one span of mi355_inflate_index left"""
+    _fields_ = [("start", C.c_uint64), ("end_bit", C.c_uint64), ("count", C.c_uint64), ("how", C.c_uint32), ("link", C.c_uint32),
+                ("btype", C.c_uint32), ("status", C.c_uint32), ("n_stored", C.c_uint32), ("n_fixed", C.c_uint32),
+                ("n_dynamic", C.c_uint32), ("reserved", C.c_uint32), ("n_blocks", C.c_uint64), ("bit", C.c_uint64),
+                ("in_pos", C.c_uint64)]
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -284,6 +292,14 @@ def load():
     L.mi355_inflate_tabled.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport)]
     L.mi355_inflate_tabled_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_inflate_index_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t,
+                                             C.POINTER(C.c_size_t), C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_index.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t,
+                                      C.POINTER(C.c_size_t), C.POINTER(InflateReport)]
+    L.mi355_inflate_parallel_device.argtypes = L.mi355_inflate_device.argtypes
+    L.mi355_inflate_parallel.argtypes = L.mi355_inflate.argtypes
+    L.mi355_inflate_index_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_inflate_index_last_walks.argtypes = [C.c_void_p, C.POINTER(IndexWalk), C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -312,6 +328,8 @@ EXPORTED = [
     "mi355_deflate_verify", "mi355_deflate_verify_device", "mi355_deflate_verify_batch_device",
     "mi355_inflate", "mi355_inflate_device", "mi355_inflate_batch_device",
     "mi355_inflate_tabled", "mi355_inflate_tabled_device", "mi355_inflate_tabled_last_stages",
+    "mi355_inflate_index", "mi355_inflate_index_device", "mi355_inflate_parallel", "mi355_inflate_parallel_device",
+    "mi355_inflate_index_last_stages", "mi355_inflate_index_last_walks",
 ]
 
 
@@ -345,6 +363,7 @@ class Context:
     CFG_RANGE_BYTES, CFG_LONG_FROM, CFG_SORT_RANKS, CFG_HOST_STREAMING, CFG_MULTI_STITCH, CFG_STEPS_IN_EMIT = 1, 2, 3, 4, 5, 6
     CFG_HOST_BOUNCE, CFG_HOST_THREADS, CFG_STAGE_CLOCKS, CFG_BATCH_BYTES = 7, 8, 9, 10
     CFG_INFLATE_GROUP_BYTES = 11
+    CFG_INFLATE_INDEX_SPAN_BYTES = 12
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -695,15 +714,21 @@ class Context:
             self._err(rc)
 
     # ---- inflate: the stream's bytes (mi355_inflate*) ----
-    def inflate_raw(self, stream, wrapper=0, out_cap=0, blocks=None):
+    def inflate_raw(self, stream, wrapper=0, out_cap=0, blocks=None, parallel=False):
         """mi355_inflate on host bytes, nothing raised for the three outcomes of a decode: (rc, out_len, report dict, the bytes
         of the buffer that hold data).  rc is OK, E_DATA or E_OUT_TOO_SMALL; out_cap 0 hands over no buffer (the size query).
-        blocks: the table of the encode that made the stream (Context.blocks()): mi355_inflate_tabled, every entry decoded on its own."""
+        blocks: the table of the encode that made the stream (Context.blocks()): mi355_inflate_tabled, every entry decoded on its own.
+        parallel: no table is at hand, the device finds one (mi355_inflate_parallel); an error together with blocks."""
         stream = bytes(stream)
         out = (C.c_uint8 * out_cap)() if out_cap else None
         n = C.c_size_t(0)
         r = InflateReport()
-        if blocks is None:
+        if parallel:
+            if blocks is not None:
+                raise ValueError("parallel=True finds the table itself: give blocks or parallel, not both")
+            rc = load().mi355_inflate_parallel(self._h, stream, len(stream), wrapper, C.cast(out, C.c_void_p) if out_cap else None,
+                                               out_cap, C.byref(n), C.byref(r))
+        elif blocks is None:
             rc = load().mi355_inflate(self._h, stream, len(stream), wrapper, C.cast(out, C.c_void_p) if out_cap else None, out_cap,
                                       C.byref(n), C.byref(r))
         else:
@@ -715,26 +740,32 @@ class Context:
         held = min(n.value, out_cap)
         return rc, n.value, r.as_dict(), bytes(memoryview(out)[:held]) if held else b""
 
-    def inflate(self, stream, wrapper=0, out_cap=None, blocks=None):
+    def inflate(self, stream, wrapper=0, out_cap=None, blocks=None, parallel=False):
         """Host bytes in, the bytes the stream (raw / zlib / gzip by wrapper) inflates to out.  out_cap None: the size is queried
         first (one decode that stores nothing), then the stream is decoded.  Raises DeflateError(E_DATA, ...) for a stream that
-        is not valid and DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap.  blocks: as in inflate_raw."""
+        is not valid and DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap.  blocks, parallel: as in inflate_raw."""
         if out_cap is None:
-            rc, out_cap, _rep, _ = self.inflate_raw(stream, wrapper, 0, blocks)
+            rc, out_cap, _rep, _ = self.inflate_raw(stream, wrapper, 0, blocks, parallel)
             if rc == E_DATA:
                 self._err(rc)
-        rc, _n, _rep, data = self.inflate_raw(stream, wrapper, out_cap, blocks)
+        rc, _n, _rep, data = self.inflate_raw(stream, wrapper, out_cap, blocks, parallel)
         if rc != OK:
             self._err(rc)
         return data
 
-    def inflate_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, wrapper=0, stream=0, check=False, blocks=None):
+    def inflate_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, wrapper=0, stream=0, check=False, blocks=None, parallel=False):
         """mi355_inflate_device: device pointers.  Returns (rc, out_len, report dict); rc is OK, E_DATA or E_OUT_TOO_SMALL.
         Other return codes raise, and so do those two with check=True.  blocks: the table of the encode that made the stream
-        (Context.blocks()): mi355_inflate_tabled_device."""
+        (Context.blocks()): mi355_inflate_tabled_device.  parallel: mi355_inflate_parallel_device, the table found on the device; an
+        error together with blocks."""
         n = C.c_size_t(0)
         r = InflateReport()
-        if blocks is None:
+        if parallel:
+            if blocks is not None:
+                raise ValueError("parallel=True finds the table itself: give blocks or parallel, not both")
+            rc = load().mi355_inflate_parallel_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, C.c_void_p(d_out_ptr), out_cap,
+                                                      C.byref(n), C.byref(r), C.c_void_p(stream))
+        elif blocks is None:
             rc = load().mi355_inflate_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, C.c_void_p(d_out_ptr), out_cap,
                                              C.byref(n), C.byref(r), C.c_void_p(stream))
         else:
@@ -752,6 +783,48 @@ class Context:
         if rc != OK:
             self._err(rc)
         return dict(zip(("decode_ms", "windows_ms", "resolve_ms", "checksums_ms"), ms))
+
+    # ---- the table of a stream that came without one (mi355_inflate_index*) ----
+    def _index(self, call):
+        n = C.c_size_t(0)
+        r = InflateReport()
+        rc = call(None, 0, C.byref(n), C.byref(r))  # the query
+        arr = (BlockInfo * max(n.value, 1))()
+        if rc == E_OUT_TOO_SMALL:
+            rc = call(arr, n.value, C.byref(n), C.byref(r))
+        if rc != OK:
+            self._err(rc)
+        return [dict(btype=a.btype, bfinal=a.bfinal, n_lz=a.n_tokens, in_bytes=a.in_bytes, bit_start=a.bit_start) for a in arr[: n.value]]
+
+    def inflate_index(self, stream, wrapper=0):
+        """mi355_inflate_index on host bytes: the stream's block table, found on the device, in the form Context.blocks() returns --
+        what blocks= of inflate and verify takes.  Raises DeflateError(E_DATA, ...) for a stream whose walk fails."""
+        stream = bytes(stream)
+        return self._index(lambda arr, cap, n, r: load().mi355_inflate_index(self._h, stream, len(stream), wrapper, arr, cap, n, r))
+
+    def inflate_index_device(self, d_stream_ptr, stream_len, wrapper=0, stream=0):
+        """mi355_inflate_index_device: the same for a stream in device memory"""
+        return self._index(lambda arr, cap, n, r: load().mi355_inflate_index_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper,
+                                                                                   arr, cap, n, r, C.c_void_p(stream)))
+
+    def inflate_index_stages(self):
+        """mi355_inflate_index_last_stages: ms of the last index -- the find and the walk launch (HIP events; zeros without
+        CFG_STAGE_CLOCKS) and the host's link"""
+        ms = (C.c_float * 3)()
+        rc = load().mi355_inflate_index_last_stages(self._h, ms)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("find_ms", "walk_ms", "link_ms"), ms))
+
+    def inflate_index_walks(self):
+        """mi355_inflate_index_last_walks: the walkers' records of the last index, one tuple per span in IndexWalk's field order"""
+        n = C.c_size_t(0)
+        load().mi355_inflate_index_last_walks(self._h, None, 0, C.byref(n))
+        arr = (IndexWalk * max(n.value, 1))()
+        rc = load().mi355_inflate_index_last_walks(self._h, arr, n.value, C.byref(n))
+        if rc != OK:
+            self._err(rc)
+        return [tuple(getattr(a, f) for f, _t in IndexWalk._fields_) for a in arr[: n.value]]
 
     def inflate_batch_device(self, items, wrapper=0, stream=0):
         """mi355_inflate_batch_device.  items: a BatchItem array (in_ / in_len the stream, out / out_cap the buffer, e.g. the out
@@ -826,10 +899,11 @@ class InflateReports(list):
     items = None
 
 
-def inflate_bytes(stream, wrapper=0, ctx=None, blocks=None):
+def inflate_bytes(stream, wrapper=0, ctx=None, blocks=None, parallel=False):
     """The bytes `stream` (raw / zlib / gzip by wrapper) inflates to, decoded on the GPU; DeflateError(E_DATA, ...) if it is not valid.
-    blocks: the block table of the encode that made the stream, for a parallel decode (Context.inflate)."""
-    return (ctx or default_context()).inflate(stream, wrapper, blocks=blocks)
+    blocks: the block table of the encode that made the stream, for a parallel decode (Context.inflate); parallel: a parallel decode
+    of a stream from anywhere, the table found on the device."""
+    return (ctx or default_context()).inflate(stream, wrapper, blocks=blocks, parallel=parallel)
 
 
 def verify_bytes(stream, data, wrapper=0, ctx=None):

@@ -1,12 +1,14 @@
 /* A plain C program over the C ABI of include/mi355_deflate.h (what the Rust shim of INTEGRATION.md
  * binds): compresses a file on the GPU, or with -d decompresses one.
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
- *   mi355_deflate_cli -d [-raw|-zlib|-gzip] IN OUT
+ *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
  * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
  * -d / --decompress inflates IN (a raw, zlib or gzip stream by the format switch) to OUT on the GPU: mi355_inflate once without a
- * buffer for the size, once more for the bytes; exits with status 3 and the report if the stream is not valid.
+ * buffer for the size, once more for the bytes; exits with status 3 and the report if the stream is not valid.  With --parallel the
+ * two calls are mi355_inflate_parallel: the block table of the stream is found on the GPU and every entry decoded by a wave of its own
+ * (the way for one large file from anywhere); the result is the same.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
  *             -Wl,-rpath,$PWD/deflate-rs_amd -o /tmp/mi355_deflate_cli */
 #include <stdio.h>
@@ -23,7 +25,7 @@ static int fail(const char* what, int rc, mi355_deflate_ctx* ctx) {
 int main(int argc, char** argv) {
     int wrapper = 0, level = 1;
     size_t chunk = 0;
-    int verify = 0, decompress = 0;
+    int verify = 0, decompress = 0, parallel = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "-raw")) wrapper = 0;
@@ -34,11 +36,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[a], "-best")) level = 2;
         else if (!strcmp(argv[a], "--verify") || !strcmp(argv[a], "-verify")) verify = 1;
         else if (!strcmp(argv[a], "-d") || !strcmp(argv[a], "--decompress")) decompress = 1;
+        else if (!strcmp(argv[a], "--parallel") || !strcmp(argv[a], "-parallel")) parallel = 1;
         else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
-    if (argc - a != 2) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [-raw|-zlib|-gzip] IN OUT\n",
+    if (argc - a != 2 || (parallel && !decompress)) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n",
                 argv[0], argv[0]);
         return 2;
     }
@@ -58,18 +61,20 @@ int main(int argc, char** argv) {
         mi355_inflate_report r;
         size_t need = 0, got = 0;
         uint8_t* data = NULL;
-        rc = mi355_inflate(ctx, in, n, wrapper, NULL, 0, &need, &r);
+        int (*inflate)(mi355_deflate_ctx*, const uint8_t*, size_t, int, uint8_t*, size_t, size_t*, mi355_inflate_report*) =
+            parallel ? mi355_inflate_parallel : mi355_inflate;
+        rc = inflate(ctx, in, n, wrapper, NULL, 0, &need, &r);
         if (rc == MI355_E_OUT_TOO_SMALL) {
             data = (uint8_t*)malloc(need);
             if (!data) return fail("malloc", -1, NULL);
-            rc = mi355_inflate(ctx, in, n, wrapper, data, need, &got, &r);
+            rc = inflate(ctx, in, n, wrapper, data, need, &got, &r);
         }
         if (rc == MI355_E_DATA) {
             fprintf(stderr, "inflate: status %u at bit %llu, output byte %llu\n%s\n", r.status, (unsigned long long)r.bit,
                     (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
             return 3;
         }
-        if (rc) return fail("mi355_inflate", rc, ctx);
+        if (rc) return fail(parallel ? "mi355_inflate_parallel" : "mi355_inflate", rc, ctx);
         f = fopen(argv[a + 1], "wb");
         if (!f || fwrite(data, 1, got, f) != got) return fail("write output", -1, NULL);
         fclose(f);

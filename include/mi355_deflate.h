@@ -160,7 +160,12 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *   MI355_CFG_INFLATE_GROUP_BYTES  output bytes of one group of table entries of mi355_inflate_tabled[_device] (default 256 MiB;
  *                          at least 64 KiB): a group's workspace is two bytes per output byte plus 32 KiB per entry, so a longer
  *                          stream is decoded group after group.  An entry larger than this is a group of its own.  Same bytes
- *                          either way. */
+ *                          either way.
+ *   MI355_CFG_INFLATE_INDEX_SPAN_BYTES  compressed bytes of one span of mi355_inflate_index[_device] / mi355_inflate_parallel[_device]
+ *                          (default 16 KiB; 256 bytes .. 1 GiB): one wave searches a span for a block start and one walks on from
+ *                          it, so a table has one entry per span at most.  Same bytes either way.  The default is the best of a
+ *                          sweep over 16 / 32 / 64 / 128 KiB on 100 MB of text deflated by zlib at level 6: 55.5 / 70.4 / 83.1 /
+ *                          140.1 ms for the whole mi355_inflate_parallel_device call (profiles/inflate_index_bench.json). */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -172,6 +177,7 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_STAGE_CLOCKS 9
 #define MI355_CFG_BATCH_BYTES 10
 #define MI355_CFG_INFLATE_GROUP_BYTES 11
+#define MI355_CFG_INFLATE_INDEX_SPAN_BYTES 12
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
@@ -459,7 +465,7 @@ int mi355_deflate_verify_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* 
  *   disturbs no neighbour; the call returns the first failing item's status.  One decode launch for all items, one workgroup per item.
  * Speed: ONE wave walks a whole stream, symbol after symbol, so a large single stream is slow; the entry points are
  *   made for many streams at once -- pages, tiles, the items of a batch.  For one large stream whose block table was kept:
- *   mi355_inflate_tabled[_device] below. */
+ *   mi355_inflate_tabled[_device] below; for one large stream from anywhere: mi355_inflate_parallel[_device] below. */
 typedef struct {
     uint32_t status;    /* MI355_VERIFY_OK, _FRAME, _BTYPE, _STORED, _LENGTHS, _CODE, _DISTANCE, _TRUNCATED, _TRAILER, _CHECKSUM
                            (never _MISMATCH, _LENGTH: there is no input), and _TABLE from mi355_inflate_tabled* */
@@ -511,6 +517,54 @@ int mi355_inflate_tabled(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t s
  * (a wave per entry), ms[1] the window chain, ms[2] the resolve, ms[3] the checksum half of a framed call.  Zeros unless the stage
  * clocks were on for the call (MI355_CFG_STAGE_CLOCKS = 1, or 2 for tables of 32 MiB or more). */
 int mi355_inflate_tabled_last_stages(mi355_deflate_ctx* ctx, float ms[4]);
+
+/* ---- index and parallel inflate: the block table of ANY large stream, found on the device -------------------
+ * A stream that this library did not encode, or whose table was not kept -- a .gz from disk, a zlib stream from anywhere -- gets its
+ * table here.  The deflate data behind the frame header is cut into spans of MI355_CFG_INFLATE_INDEX_SPAN_BYTES compressed bytes.
+ * One wave per span finds the span's candidate: the smallest bit offset in it at which a NON-FINAL DYNAMIC block with a valid header
+ * (the rules of MI355_VERIFY_LENGTHS) begins, the header wholly inside the stream; span 0's candidate is the first deflate bit.  One
+ * wave per candidate then decodes from it on, counting and storing nothing, until it stands on the candidate of a later span, behind
+ * the BFINAL block or at a failure.  The host follows the links from span 0: that chain is the stream's one serial walk, and its
+ * walkers are the table's entries.  Stored and fixed blocks are not searched for, so a stretch without a non-final dynamic block
+ * start (fixed only, stored only, one Huffman-only block) is ONE entry walked by one wave and costs what mi355_inflate costs.
+ * mi355_inflate_index[_device]: the table, in HOST memory, as mi355_inflate_tabled and mi355_deflate_verify take it: bit_start,
+ *   in_bytes, btype of the entry's first block, bfinal = 1 on the last entry of a chain that reached the BFINAL block, the other
+ *   fields 0.  *n_blocks = the count, never more than the number of spans; cap too small: MI355_E_OUT_TOO_SMALL and the count needed
+ *   (cap == 0 with blocks == NULL is the query).  A stream whose chain fails: MI355_E_DATA, the entries up to and including the failing
+ *   link (its in_bytes = the bytes counted in front of the failure) and the failure in the report, out_pos = the bytes in front of
+ *   it.  What the index cannot see -- a distance that reaches in front of the stream, bytes behind the BFINAL block, the checksum --
+ *   the decode judges.  Wrappers and frame rules, MI355_E_ARG (decided before a context or the device is touched) / _STATE / _HIP:
+ *   the tabled call's; more than 2^31 - 1 spans are MI355_E_UNSUPPORTED.  last_info / last_blocks / last_batch_info are left alone.
+ * mi355_inflate_parallel[_device]: the index, then the tabled inflate from its table (a table of one entry: mi355_inflate itself).
+ *   The contract is mi355_inflate[_device]'s on every stream, valid or not: return value, *out_len, every report field but ms, the
+ *   bytes of out, nothing at or beyond out_pos or out_cap.  The tabled pass refuses a table that is not the serial walk, so a wrong
+ *   candidate costs time and never a byte. */
+int mi355_inflate_index_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, int wrapper, mi355_block_info* blocks,
+                               size_t cap, size_t* n_blocks, mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_index(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, int wrapper, mi355_block_info* blocks, size_t cap,
+                        size_t* n_blocks, mi355_inflate_report* report);
+int mi355_inflate_parallel_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, int wrapper, void* d_out, size_t out_cap,
+                                  size_t* out_len, mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_parallel(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, int wrapper, uint8_t* out, size_t out_cap,
+                           size_t* out_len, mi355_inflate_report* report);
+/* Diagnostics, measuring aids like mi355_inflate_tabled_last_stages and no part of the stable interface.  _last_stages: milliseconds of
+ * the context's last index: ms[0] the find launch, ms[1] the walk launch (HIP events; zeros unless the stage clocks were on), ms[2]
+ * the host's link.  _last_walks: the walkers' records of the last index, one per span of the whole stream's length. */
+typedef struct {
+    uint64_t start;    /* the span's candidate, a raw-deflate bit offset; UINT64_MAX: none */
+    uint64_t end_bit;  /* where the walk stopped */
+    uint64_t count;    /* output bytes counted */
+    uint32_t how;      /* 0 linked to span `link`, 1 behind the BFINAL block, 2 failed, 3 no candidate */
+    uint32_t link;
+    uint32_t btype;    /* of the first block */
+    uint32_t status;   /* the failure: MI355_VERIFY_* */
+    uint32_t n_stored, n_fixed, n_dynamic, reserved;
+    uint64_t n_blocks;
+    uint64_t bit;      /* the failure's bit */
+    uint64_t in_pos;   /* ... and the bytes counted in front of it */
+} mi355_index_walk; /* 80 bytes */
+int mi355_inflate_index_last_stages(mi355_deflate_ctx* ctx, float ms[3]);
+int mi355_inflate_index_last_walks(mi355_deflate_ctx* ctx, mi355_index_walk* out, size_t cap, size_t* n_spans);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range

@@ -73,6 +73,25 @@ extern "C" {
                                          hdrs: *const std::ffi::c_void, n_hdrs: usize, arena: *mut u8, arena_cap: usize, align: usize,
                                          arena_used: *mut usize) -> c_int;
     fn mi355_device_count() -> c_int; // (the shim links libmi355deflate.so only: no HIP symbol is named from Rust)
+    // one large stream from anywhere decoded in parallel, its block table found on the GPU (include/mi355_deflate.h, "index and
+    // parallel inflate"): declarations only, the reference has no decoder to mirror.  report: mi355_inflate_report, 56 bytes;
+    // blocks: mi355_block_info, 32 bytes each
+    #[allow(dead_code)]
+    fn mi355_inflate_parallel(ctx: *mut Ctx, stream: *const u8, stream_len: usize, wrapper: c_int, out: *mut u8, out_cap: usize,
+                              out_len: *mut usize, report: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mi355_inflate_parallel_device(ctx: *mut Ctx, d_stream: *const std::ffi::c_void, stream_len: usize, wrapper: c_int,
+                                     d_out: *mut std::ffi::c_void, out_cap: usize, out_len: *mut usize,
+                                     report: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mi355_inflate_index(ctx: *mut Ctx, stream: *const u8, stream_len: usize, wrapper: c_int, blocks: *mut std::ffi::c_void,
+                           cap: usize, n_blocks: *mut usize, report: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mi355_inflate_index_device(ctx: *mut Ctx, d_stream: *const std::ffi::c_void, stream_len: usize, wrapper: c_int,
+                                  blocks: *mut std::ffi::c_void, cap: usize, n_blocks: *mut usize, report: *mut std::ffi::c_void,
+                                  hip_stream: *mut std::ffi::c_void) -> c_int;
+    #[allow(dead_code)]
+    fn mi355_inflate_index_last_stages(ctx: *mut Ctx, ms: *mut f32) -> c_int;
 }
 
 /// Inputs of at least this many bytes are cut over all GPUs of the node by the one-shot functions (below it one GPU is
