@@ -702,6 +702,16 @@ void launch_crc(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint6
         hipLaunchKernelGGL(k_crc_fold, dim3(cdiv(nch, 256)), dim3(256), 0, st, (uint32_t)n, nch, part, c->d_sc);
     }
 }
+// One run of bytes outside an encode, wrapper 1: Adler-32, 2: CRC-32, into the cleared scalars; the CRC's words in the context's own
+// d_crc (the checksum entries below and the decode side, decode_host.inc: the workspace may belong to a live shard)
+int launch_sums_one(mi355_deflate_ctx* c, hipStream_t st, int wrapper, const uint8_t* d_in, uint64_t n) {
+    if (wrapper == 2)
+        if (const int rc = ensure_buf(c, &c->d_crc, &c->d_crc_cap, ((size_t)cdiv(n, CRC_CHUNK) + 2) * 4 + 512)) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
+    if (wrapper == 1) launch_adler(c, st, d_in, n);
+    if (wrapper == 2) launch_crc(c, st, d_in, n, reinterpret_cast<uint32_t*>(c->d_crc));
+    return MI355_OK;
+}
 // The checksum of the input and the frame around the stream (wrapper 1: zlib, 2: gzip with the caller's header; `final`: with the trailer).
 int launch_frame_tail(mi355_deflate_ctx* c, hipStream_t st, const uint8_t* d_in, uint64_t n, uint32_t wrapper, const Workspace& w,
                       const uint8_t* gz_hdr, size_t gz_len, uint8_t* d_out, bool final) {
@@ -1967,8 +1977,7 @@ int mi355_adler32_device(mi355_deflate_ctx* c, const void* d_in, size_t n, uint3
     if (!adler || (!d_in && n) || n >= 0xFFFF0000ull) return MI355_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
-    HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    launch_adler(c, st, reinterpret_cast<const uint8_t*>(d_in), n);
+    if (const int rc = launch_sums_one(c, st, 1, reinterpret_cast<const uint8_t*>(d_in), n)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     *adler = c->h_sc->adler;
@@ -1982,12 +1991,7 @@ int mi355_crc32_device(mi355_deflate_ctx* c, const void* d_in, size_t n, uint32_
     if (!crc || (!d_in && n) || n >= 0xFFFF0000ull) return MI355_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
-    uint32_t nch = cdiv(n, CRC_CHUNK);
-    int rc = ensure_buf(c, &c->d_crc, &c->d_crc_cap, ((size_t)nch + 2) * 4 + 512);
-    if (rc) return rc;
-    uint32_t* part = reinterpret_cast<uint32_t*>(c->d_crc);
-    HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    launch_crc(c, st, reinterpret_cast<const uint8_t*>(d_in), n, part);
+    if (const int rc = launch_sums_one(c, st, 2, reinterpret_cast<const uint8_t*>(d_in), n)) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_sc, c->d_sc, sizeof(DevScalars), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     *crc = c->h_sc->crc;

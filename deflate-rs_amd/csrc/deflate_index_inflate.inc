@@ -5,7 +5,7 @@
 //   k_index_walk  one workgroup of one wave per span that has a candidate: k_inflate's scalar chain, counting, until it meets the
 //                 candidate of a later span, the BFINAL block's end or a failure
 // The records come back with one wait; the chain from span 0 is the table.  mi355_inflate_parallel hands it to the tabled driver of
-// deflate_table_inflate.inc, which judges it: DESIGN.md section 14.
+// deflate_table_inflate.inc, which judges it.  The host driver's shared steps are in decode_host.inc.  DESIGN.md section 14.
 #include "inflate_index.h"
 
 namespace mi355 {
@@ -48,13 +48,9 @@ namespace {
 static_assert(sizeof(ix::Walk) == 80 && sizeof(mi355_index_walk) == 80, "mi355_index_walk mirrors ix::Walk");
 static_assert(ix::SPAN_DEFAULT == 16384 && ix::SPAN_MIN == 256 && ix::SPAN_MAX == (1ull << 30), "the setting's default and range");
 
-// one stream, device resident: its table (the chain's entries, a failing last link included) and its record
+// one stream, device resident (the entry has asked shard_refusal): its table (the chain's entries, a failing last link included), its record
 int index_run(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, int wrapper, hipStream_t st, std::vector<mi355_block_info>& table,
               iw::Rec& acc) {
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
     const uint64_t S = c->index_span;
     const uint64_t n_spans = ix::ix_n_spans(stream_len, S);  // (of the whole stream: the frame's bytes make a span too many at most)
     if (n_spans > 0x7fffffffull) {
@@ -65,36 +61,22 @@ int index_run(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, 
     const size_t rec_at = align_up(sizeof(uint64_t) * n_spans, 256);
     int rc = verify_room(c, rec_at + sizeof(ix::Walk) * n_spans);
     if (rc) return rc;
-    const bool clocks = stage_clocks_on(c, stream_len);
-    for (int k = 0; k < 3; k++) c->x_ms[k] = 0;
-    if (clocks && !c->x_ev_ok) {  // all three or none
-        hipEvent_t ev[3];
-        for (int k = 0; k < 3; k++) {
-            const hipError_t e = hipEventCreate(&ev[k]);
-            if (e == hipSuccess) continue;
-            for (int j = 0; j < k; j++) (void)hipEventDestroy(ev[j]);
-            HIPCHK(c, e);
-        }
-        for (int k = 0; k < 3; k++) c->x_ev[k] = ev[k];
-        c->x_ev_ok = true;
-    }
-    const auto mark = [&](int k) { return clocks ? hipEventRecord(c->x_ev[k], st) : hipSuccess; };
+    StageClocks<3> clk{c->x_ev, c->x_ev_ok, c->x_ms, st, stage_clocks_on(c, stream_len)};
+    rc = clk.begin(c);
+    if (rc) return rc;
     const XItem item{d_stream, stream_len, S, n_spans, (uint32_t)wrapper, 0u};
     uint64_t* d_cand = reinterpret_cast<uint64_t*>(c->v_dev);
     ix::Walk* d_recs = reinterpret_cast<ix::Walk*>(c->v_dev + rec_at);
-    HIPCHK(c, mark(0));
+    HIPCHK(c, clk.mark(0));
     hipLaunchKernelGGL(k_index_find, dim3((uint32_t)n_spans), dim3(64), 0, st, item, d_cand);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, mark(1));
+    HIPCHK(c, clk.mark(1));
     hipLaunchKernelGGL(k_index_walk, dim3((uint32_t)n_spans), dim3(64), 0, st, item, d_cand, d_recs);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, mark(2));
+    HIPCHK(c, clk.mark(2));
     HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(ix::Walk) * n_spans, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));  // the one wait of an index
-    for (int k = 0; k < 2; k++) {
-        float ms = 0;
-        if (clocks && hipEventElapsedTime(&ms, c->x_ev[k], c->x_ev[k + 1]) == hipSuccess) c->x_ms[k] = ms;
-    }
+    clk.lap(0, 1, 0), clk.lap(1, 2, 1);
     const auto t0 = std::chrono::steady_clock::now();
     const ix::Walk* w = reinterpret_cast<const ix::Walk*>(c->v_host + rec_at);
     c->x_walks.assign(c->v_host + rec_at, c->v_host + rec_at + sizeof(ix::Walk) * n_spans);
@@ -108,10 +90,6 @@ int index_run(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, 
     }
     c->x_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return MI355_OK;
-}
-
-bool index_args_bad(const void* stream, size_t stream_len, int wrapper, const mi355_inflate_report* report) {
-    return !report || (!stream && stream_len) || wrapper < 0 || wrapper > 2;
 }
 
 // the table and the report of an index call handed to the caller
@@ -130,7 +108,7 @@ int index_give(mi355_deflate_ctx* c, const std::vector<mi355_block_info>& table,
     return rc;
 }
 
-// the index, then the decode it allows: a table of one entry is the one-wave inflate itself
+// the index, then the decode it allows, behind the entry's checks: a table of one entry is the one-wave inflate itself
 int parallel_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, int wrapper, uint8_t* d_out, size_t out_cap, size_t* out_len,
                  mi355_inflate_report* report, hipStream_t st, uint64_t* valid) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -157,33 +135,32 @@ extern "C" {
 
 int mi355_inflate_index_device(mi355_deflate_ctx* c, const void* d_stream, size_t stream_len, int wrapper, mi355_block_info* blocks, size_t cap,
                                size_t* n_blocks, mi355_inflate_report* report, void* hip_stream) {
-    if (index_args_bad(d_stream, stream_len, wrapper, report) || !n_blocks || (!blocks && cap)) return tabled_refuse(c, "inflate index: bad argument");
+    if (inflate_args_bad(d_stream, stream_len, wrapper, blocks, cap, n_blocks, report)) return tabled_refuse(c, "inflate index: bad argument");
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    if (const int rc = shard_refusal(c)) return rc;
     std::vector<mi355_block_info> table;
     iw::Rec acc;
-    const int rc = index_run(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, st, table, acc);
-    if (rc) return rc;
+    if (const int rc = index_run(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, call_stream(c, hip_stream), table, acc))
+        return rc;
     return index_give(c, table, acc, blocks, cap, n_blocks, report, t0);
 }
 
+// host buffers: the stream into the context's staging; no output buffer and a table to hand back: not the shape of staged_call
 int mi355_inflate_index(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, mi355_block_info* blocks, size_t cap,
                         size_t* n_blocks, mi355_inflate_report* report) {
-    if (index_args_bad(stream, stream_len, wrapper, report) || !n_blocks || (!blocks && cap)) return tabled_refuse(c, "inflate index: bad argument");
+    if (inflate_args_bad(stream, stream_len, wrapper, blocks, cap, n_blocks, report)) return tabled_refuse(c, "inflate index: bad argument");
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     const auto t0 = std::chrono::steady_clock::now();
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
+    int rc = shard_refusal(c);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
+    rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
     if (rc) return rc;
     hipStream_t st = c->own_stream;
     if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
@@ -199,42 +176,27 @@ int mi355_inflate_index(mi355_deflate_ctx* c, const uint8_t* stream, size_t stre
 
 int mi355_inflate_parallel_device(mi355_deflate_ctx* c, const void* d_stream, size_t stream_len, int wrapper, void* d_out, size_t out_cap,
                                   size_t* out_len, mi355_inflate_report* report, void* hip_stream) {
-    if (index_args_bad(d_stream, stream_len, wrapper, report) || !out_len || (!d_out && out_cap)) return tabled_refuse(c, "inflate: bad argument");
+    if (inflate_args_bad(d_stream, stream_len, wrapper, d_out, out_cap, out_len, report)) return tabled_refuse(c, "inflate: bad argument");
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    if (const int rc = shard_refusal(c)) return rc;
     uint64_t valid = 0;
     return parallel_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, reinterpret_cast<uint8_t*>(d_out), out_cap, out_len,
-                        report, st, &valid);
+                        report, call_stream(c, hip_stream), &valid);
 }
 
+// host buffers: staged_call around the index and the decode
 int mi355_inflate_parallel(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, uint8_t* out, size_t out_cap,
                            size_t* out_len, mi355_inflate_report* report) {
-    if (index_args_bad(stream, stream_len, wrapper, report) || !out_len || (!out && out_cap)) return tabled_refuse(c, "inflate: bad argument");
+    if (inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report)) return tabled_refuse(c, "inflate: bad argument");
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
-    if (rc) return rc;
-    rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_cap + 64);
-    if (rc) return rc;
-    hipStream_t st = c->own_stream;
-    if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
-    uint64_t valid = 0;
-    rc = parallel_one(c, c->d_in, stream_len, wrapper, out_cap ? c->d_out : nullptr, out_cap, out_len, report, st, &valid);
-    if (rc != MI355_OK && rc != MI355_E_DATA && rc != MI355_E_OUT_TOO_SMALL) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
-        return rc;
-    }
-    if (valid) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)valid, hipMemcpyDeviceToHost));
-    return rc;
+    return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
+        return parallel_one(c, d_stream, stream_len, wrapper, d_out, out_cap, out_len, report, st, valid);
+    });
 }
 
 // HIP-event milliseconds of the context's last index per launch, and the host clock over its link: find, walk, link; the first two

@@ -1,7 +1,8 @@
 // Inflate (include/mi355_deflate.h mi355_inflate[_device], mi355_inflate_batch_device): decode a stream, or a batch of them, to its
 // bytes in device memory.  k_inflate runs inflate_write.h as one wave per stream -- the scalar chain of k_verify with the lanes
 // storing where verify's compare -- and, for a framed stream, the checksum kernels of the encode run over the OUTPUT afterwards and
-// k_inflate_trailer compares them with the trailer.  tests/inflwrite/ builds the same text for the host.  DESIGN.md section 12.
+// k_inflate_trailer compares them with the trailer.  tests/inflwrite/ builds the same text for the host.  The host driver's shared
+// steps are in decode_host.inc.  DESIGN.md section 12.
 #include "inflate_write.h"
 
 namespace mi355 {
@@ -77,33 +78,51 @@ void inflate_say(mi355_deflate_ctx* c, const mi355_inflate_report& r, int rc, co
 
 int inflate_rc(int iw_rc) { return iw_rc == iw::IW_OK ? MI355_OK : iw_rc == iw::IW_DATA ? MI355_E_DATA : MI355_E_OUT_TOO_SMALL; }
 
+// the arguments every single-stream decode entry refuses; out / out_cap / out_len are the table's of an index call
+bool inflate_args_bad(const void* stream, size_t stream_len, int wrapper, const void* out, size_t out_cap, const size_t* out_len,
+                      const mi355_inflate_report* report) {
+    return !report || !out_len || (!stream && stream_len) || (!out && out_cap) || wrapper < 0 || wrapper > 2;
+}
+
+// The end of a framed call, around the checksum launches over the outputs that are clean and fit (sums()): k_inflate_trailer over the
+// k records at rec_at of the descriptor room, whose items are at its front, the records back, the wait.  mark(0) and mark(1) stand
+// around the launches (the tabled driver's stage clock).
+template <class Sums, class Mark>
+int framed_tail(mi355_deflate_ctx* c, hipStream_t st, size_t k, size_t rec_at, Sums sums, Mark mark) {
+    HIPCHK(c, mark(0));
+    const int rc = sums();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_inflate_trailer, dim3(cdiv(k, 64)), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
+                       reinterpret_cast<iw::Rec*>(c->v_dev + rec_at), (uint32_t)k);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, mark(1));
+    HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return MI355_OK;
+}
+
 // k streams, device resident.  The decode launch, the records back (the one wait of a raw call); framed: the checksum launches over
-// the outputs that are clean and fit -- `one`: k_adler_part / k_crc_part + fold into the context's scalars, else kb_adler_part /
-// kb_crc over one flat grid --, k_inflate_trailer, the records back again.  fill(j, item): the j-th stream.  The records are left
-// in c->v_host at the offset returned in *recs_at.
+// the outputs that are clean and fit -- `one`: launch_sums_one into the context's scalars, else the batch's plan over one flat grid
+// --, and framed_tail.  fill(j, item): the j-th stream.  The records are left in c->v_host, *recs_out.
 template <class Fill>
 int inflate_run(mi355_deflate_ctx* c, size_t k, int wrapper, bool one, hipStream_t st, Fill fill, const iw::Rec** recs_out) {
-    // [IItem k] | [BatchItem k][running sums BS_N x (k + 1)] | [DevState k] | [Rec k]
+    // [IItem k] and, for a framed batch, the checksum plan behind them
     const bool batch_sums = wrapper && !one;
-    const size_t bat_at = align_up(sizeof(IItem) * k, 256);
-    const size_t pre_at = bat_at + (batch_sums ? sizeof(BatchItem) * k : 0);
-    const size_t st_at = align_up(pre_at + (batch_sums ? sizeof(uint32_t) * BS_N * (k + 1) : 0), 256);
-    const size_t rec_at = align_up(st_at + (batch_sums ? sizeof(DevState) * k : 0), 256);
-    int rc = verify_room(c, rec_at + sizeof(iw::Rec) * k);
+    const BatchSums plan(sizeof(IItem) * k, k, batch_sums, sizeof(iw::Rec));
+    const size_t rec_at = plan.rec_at;
+    int rc = verify_room(c, plan.bytes);
     if (rc) return rc;
     IItem* hit = reinterpret_cast<IItem*>(c->v_host);
-    DevState* dst = reinterpret_cast<DevState*>(c->v_dev + st_at);
     for (size_t j = 0; j < k; j++) {
         fill(j, hit[j]);
-        hit[j].sc = !wrapper ? nullptr : one ? c->d_sc : &dst[j].sc;
+        hit[j].sc = !wrapper ? nullptr : one ? c->d_sc : &plan.states(c)[j].sc;
         hit[j].wrapper = (uint32_t)wrapper, hit[j].pad = 0;
     }
-    const IItem* d_items = reinterpret_cast<const IItem*>(c->v_dev);
-    iw::Rec* d_recs = reinterpret_cast<iw::Rec*>(c->v_dev + rec_at);
     const iw::Rec* recs = reinterpret_cast<const iw::Rec*>(c->v_host + rec_at);
     *recs_out = recs;
-    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, bat_at, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_inflate, dim3((uint32_t)k), dim3(64), 0, st, d_items, d_recs);
+    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, plan.bat_at, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_inflate, dim3((uint32_t)k), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
+                       reinterpret_cast<iw::Rec*>(c->v_dev + rec_at));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -116,56 +135,24 @@ int inflate_run(mi355_deflate_ctx* c, size_t k, int wrapper, bool one, hipStream
             judged++;
         }
     if (!judged) return MI355_OK;
-    if (one) {
-        const uint64_t n = recs[0].out_len;
-        if (wrapper == 2) {
-            rc = ensure_buf(c, &c->d_crc, &c->d_crc_cap, ((size_t)cdiv(n, CRC_CHUNK) + 2) * 4 + 512);
+    return framed_tail(
+        c, st, k, rec_at,
+        [&]() {
+            if (one) return launch_sums_one(c, st, wrapper, hit[0].out, recs[0].out_len);
+            const int rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* n) {
+                *p = hit[j].out, *n = iw::iw_judged(recs[j], (uint32_t)wrapper, hit[j].cap) ? recs[j].out_len : 0;
+            });
             if (rc) return rc;
-        }
-        HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-        if (wrapper == 1) launch_adler(c, st, hit[0].out, n);
-        if (wrapper == 2) launch_crc(c, st, hit[0].out, n, reinterpret_cast<uint32_t*>(c->d_crc));
-    } else {
-        BatchItem* hb = reinterpret_cast<BatchItem*>(c->v_host + bat_at);
-        uint32_t* hpre = reinterpret_cast<uint32_t*>(c->v_host + pre_at);
-        memset(c->v_host + bat_at, 0, st_at - bat_at);
-        for (size_t j = 0; j < k; j++) {
-            const bool on = iw::iw_judged(recs[j], (uint32_t)wrapper, hit[j].cap);
-            const uint64_t n = on ? recs[j].out_len : 0;
-            hb[j].in = hit[j].out;
-            hb[j].n = (uint32_t)n;
-            hb[j].st = dst + j;
-            const uint64_t wg[2] = {cdiv(n, ADLER_CHUNK), cdiv(n, 256 * CRC_CHUNK)};
-            for (uint32_t s = 0; s < 2; s++) {
-                const size_t row = (size_t)(s ? BS_CRC : BS_ADLER) * (k + 1);
-                const uint64_t t = (uint64_t)hpre[row + j] + wg[s];
-                if (t > 0x7fffffffull) return MI355_E_ARG;
-                hpre[row + j + 1] = (uint32_t)t;
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(c->v_dev + bat_at, c->v_host + bat_at, st_at - bat_at, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemsetAsync(dst, 0, sizeof(DevState) * k, st));
-        const BatchArgs a{reinterpret_cast<const BatchItem*>(c->v_dev + bat_at), reinterpret_cast<const uint32_t*>(c->v_dev + pre_at), (uint32_t)k};
-        const uint32_t grid = hpre[(size_t)(wrapper == 1 ? BS_ADLER : BS_CRC) * (k + 1) + k];
-        if (grid && wrapper == 1) hipLaunchKernelGGL(kb_adler_part, dim3(grid), dim3(256), 0, st, a);
-        if (grid && wrapper == 2) hipLaunchKernelGGL(kb_crc, dim3(grid), dim3(256), 0, st, a);
-    }
-    hipLaunchKernelGGL(k_inflate_trailer, dim3(cdiv(k, 64)), dim3(64), 0, st, d_items, d_recs, (uint32_t)k);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return MI355_OK;
+            HIPCHK(c, hipMemcpyAsync(c->v_dev + plan.bat_at, c->v_host + plan.bat_at, plan.st_at - plan.bat_at, hipMemcpyHostToDevice, st));
+            return plan.launch(c, wrapper, st);
+        },
+        [](int) { return hipSuccess; });
 }
 
-// one stream, device resident; *valid: the bytes of d_out that hold data
+// one stream, device resident, its arguments checked by the entry; *valid: the bytes of d_out that hold data
 int inflate_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, int wrapper, uint8_t* d_out, size_t out_cap, size_t* out_len,
                 mi355_inflate_report* report, hipStream_t st, uint64_t* valid) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!report || !out_len || (!d_stream && stream_len) || (!d_out && out_cap) || wrapper < 0 || wrapper > 2) return MI355_E_ARG;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
     const iw::Rec* recs = nullptr;
     int rc = inflate_run(c, 1, wrapper, true, st,
                          [&](size_t, IItem& it) { it.stream = d_stream, it.stream_len = stream_len, it.out = d_out, it.cap = out_cap; }, &recs);
@@ -187,38 +174,23 @@ int mi355_inflate_device(mi355_deflate_ctx* c, const void* d_stream, size_t stre
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    if (inflate_args_bad(d_stream, stream_len, wrapper, d_out, out_cap, out_len, report)) return MI355_E_ARG;
+    if (const int rc = shard_refusal(c)) return rc;
     uint64_t valid = 0;
     return inflate_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, reinterpret_cast<uint8_t*>(d_out), out_cap, out_len,
-                       report, st, &valid);
+                       report, call_stream(c, hip_stream), &valid);
 }
 
-// host buffers: the stream goes into the context's staging with a plain copy, the bytes that hold data come back with one
+// host buffers: staged_call around the one-wave worker
 int mi355_inflate(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, uint8_t* out, size_t out_cap, size_t* out_len,
                   mi355_inflate_report* report) {
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    if (!report || !out_len || (!stream && stream_len) || (!out && out_cap) || wrapper < 0 || wrapper > 2) return MI355_E_ARG;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
-    if (rc) return rc;
-    rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_cap + 64);
-    if (rc) return rc;
-    hipStream_t st = c->own_stream;
-    if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
-    uint64_t valid = 0;
-    rc = inflate_one(c, c->d_in, stream_len, wrapper, out_cap ? c->d_out : nullptr, out_cap, out_len, report, st, &valid);
-    if (rc != MI355_OK && rc != MI355_E_DATA && rc != MI355_E_OUT_TOO_SMALL) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
-        return rc;
-    }
-    if (valid) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)valid, hipMemcpyDeviceToHost));
-    return rc;
+    if (inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report)) return MI355_E_ARG;
+    return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
+        return inflate_one(c, d_stream, stream_len, wrapper, d_out, out_cap, out_len, report, st, valid);
+    });
 }
 
 // one decode launch for all items, one workgroup per item; the framed items' checksums over one flat grid behind it
@@ -228,48 +200,29 @@ int mi355_inflate_batch_device(mi355_deflate_ctx* c, mi355_batch_item* items, si
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     const auto t0 = std::chrono::steady_clock::now();
-    if ((!items && n_items) || wrapper < 0 || wrapper > 2 || n_items > 0x7fffffffull) return MI355_E_ARG;
     std::vector<uint32_t> act;
-    for (size_t i = 0; i < n_items; i++) {
-        if (items[i].status != MI355_OK) continue;  // skipped, left alone
-        if ((!items[i].in && items[i].in_len) || (!items[i].out && items[i].out_cap)) return MI355_E_ARG;
-        act.push_back((uint32_t)i);
-    }
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    if (act.empty()) return MI355_OK;
+    int rc = batch_active(c, items, n_items, wrapper, act, [](const mi355_batch_item& it) { return !it.out && it.out_cap ? MI355_E_ARG : MI355_OK; });
+    if (rc || act.empty()) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
     const iw::Rec* recs = nullptr;
-    int rc = inflate_run(c, act.size(), wrapper, false, st,
-                         [&](size_t j, IItem& it) {
-                             const mi355_batch_item& b = items[act[j]];
-                             it.stream = reinterpret_cast<const uint8_t*>(b.in), it.stream_len = b.in_len;
-                             it.out = reinterpret_cast<uint8_t*>(b.out), it.cap = b.out_cap;
-                         },
-                         &recs);
+    rc = inflate_run(c, act.size(), wrapper, false, call_stream(c, hip_stream),
+                     [&](size_t j, IItem& it) {
+                         const mi355_batch_item& b = items[act[j]];
+                         it.stream = reinterpret_cast<const uint8_t*>(b.in), it.stream_len = b.in_len;
+                         it.out = reinterpret_cast<uint8_t*>(b.out), it.cap = b.out_cap;
+                     },
+                     &recs);
     if (rc) return rc;
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    int first = MI355_OK;
-    for (size_t j = 0; j < act.size(); j++) {
-        mi355_batch_item& b = items[act[j]];
-        mi355_inflate_report r;
-        uint64_t valid = 0;
-        const int s = inflate_rc(iw::iw_report(recs[j], b.out_cap, r, &valid));
-        r.ms = ms;
-        if (reports) reports[act[j]] = r;
-        b.status = s;
-        b.out_len = s == MI355_E_DATA ? (size_t)valid : (size_t)r.out_len;
-        if (s != MI355_OK && first == MI355_OK) {
-            first = s;
-            char what[48];
-            snprintf(what, sizeof what, "inflate: item %u", act[j]);
-            inflate_say(c, r, s, what);
-        }
-    }
-    return first;
+    return batch_give(
+        items, act, reports, ms, "inflate",
+        [&](size_t j, mi355_batch_item& b, mi355_inflate_report& r) {
+            uint64_t valid = 0;
+            const int s = inflate_rc(iw::iw_report(recs[j], b.out_cap, r, &valid));
+            b.out_len = s == MI355_E_DATA ? (size_t)valid : (size_t)r.out_len;
+            return s;
+        },
+        [&](const mi355_inflate_report& r, int s, const char* what) { inflate_say(c, r, s, what); });
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 //   k_inflate_tab          one workgroup of one wave per entry: the scalar chain of k_inflate, 16-bit symbols where it has bytes
 //   k_inflate_tab_window   ONE workgroup: the resolved 32 KiB window behind every entry of the group, one entry a step
 //   k_inflate_tab_resolve  flat over the output: bytes from symbols and windows -- the only kernel that writes `out`
-// and then the checksum launches over the output and k_inflate_trailer, as in deflate_inflate.inc.  DESIGN.md section 13.
+// and then the checksum launches over the output and k_inflate_trailer: framed_tail of deflate_inflate.inc.  The host driver's shared
+// steps are in decode_host.inc.  DESIGN.md section 13.
 #include "inflate_table.h"
 
 namespace mi355 {
@@ -113,7 +114,7 @@ namespace {
 // what is wrong with a tabled call's arguments, or nullptr: decided from the arguments alone, before a context or the device is touched
 const char* tabled_args(const void* stream, size_t stream_len, int wrapper, const mi355_block_info* blocks, size_t n_blocks, const void* out,
                         size_t out_cap, const size_t* out_len, const mi355_inflate_report* report, uint64_t* total) {
-    if (!report || !out_len || (!stream && stream_len) || (!out && out_cap) || wrapper < 0 || wrapper > 2) return "inflate: bad argument";
+    if (inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report)) return "inflate: bad argument";
     if (n_blocks > 0x7fffffffull) return "inflate: the table is too long";
     // (entry 0 begins where the stream begins: the first link of the chain that makes a passing table the stream's serial walk)
     if (n_blocks && blocks[0].bit_start != 0) return "inflate: the table's first entry does not begin at bit 0";
@@ -134,16 +135,12 @@ int tabled_refuse(mi355_deflate_ctx* c, const char* why) {
     return MI355_E_ARG;
 }
 
-// one stream with a table, device resident (the arguments have passed tabled_args; total: the sum of the table's in_bytes);
-// *valid: the bytes of d_out that hold data
+// one stream with a table, device resident (the arguments have passed tabled_args and the context shard_refusal; total: the sum of
+// the table's in_bytes); *valid: the bytes of d_out that hold data
 int inflate_tabled_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, int wrapper, const mi355_block_info* blocks,
                        size_t n_blocks, uint64_t total, uint8_t* d_out, size_t out_cap, size_t* out_len, mi355_inflate_report* report,
                        hipStream_t st, uint64_t* valid) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
     std::vector<ic::Entry> ents(n_blocks);
     ic::ic_make_entries([&](uint64_t k) { return blocks[k].bit_start; }, [&](uint64_t k) { return blocks[k].in_bytes; }, n_blocks, 0u, ents.data());
     const uint64_t cap = out_cap;
@@ -167,25 +164,10 @@ int inflate_tabled_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t str
     // descriptors: [Entry n] | [limit] [Rec n]
     rc = verify_room(c, align_up(align_up(sizeof(ic::Entry) * n_max, 256) + 256 + sizeof(ic::Rec) * n_max, 256) + 512);
     if (rc) return rc;
-    // HIP-event time per launch kind, only when asked (MI355_CFG_STAGE_CLOCKS): an event is idle queue between two kernels
-    const bool clocks = stage_clocks_on(c, total);
-    for (int k = 0; k < 4; k++) c->t_ms[k] = 0;
-    if (clocks && !c->t_ev_ok) {  // all four or none: what was made before a failure is destroyed again
-        hipEvent_t ev[4];
-        for (int k = 0; k < 4; k++) {
-            const hipError_t e = hipEventCreate(&ev[k]);
-            if (e == hipSuccess) continue;
-            for (int j = 0; j < k; j++) (void)hipEventDestroy(ev[j]);
-            HIPCHK(c, e);
-        }
-        for (int k = 0; k < 4; k++) c->t_ev[k] = ev[k];
-        c->t_ev_ok = true;
-    }
-    const auto mark = [&](int k) { return clocks ? hipEventRecord(c->t_ev[k], st) : hipSuccess; };
-    const auto lap = [&](int from, int to, int what) {
-        float ms = 0;
-        if (clocks && hipEventElapsedTime(&ms, c->t_ev[from], c->t_ev[to]) == hipSuccess) c->t_ms[what] += ms;
-    };
+    // HIP-event time per launch kind
+    StageClocks<4> clk{c->t_ev, c->t_ev_ok, c->t_ms, st, stage_clocks_on(c, total)};
+    rc = clk.begin(c);
+    if (rc) return rc;
     bool first = true;
     for (uint64_t k0 = 0, k1, base, stored; k0 < n_blocks; k0 = k1) {
         group(k0, k1, base, stored);
@@ -200,50 +182,37 @@ int inflate_tabled_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t str
         HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, sizeof(ic::Entry) * n, hipMemcpyHostToDevice, st));
         if (first) HIPCHK(c, hipMemsetAsync(c->t_dev, 0, it::WIN, st));  // (nothing refers to the window in front of the stream)
         first = false;
-        HIPCHK(c, mark(0));
+        HIPCHK(c, clk.mark(0));
         hipLaunchKernelGGL(k_inflate_tab, dim3(n), dim3(64), 0, st, item, d_ents, d_recs);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, mark(1));
+        HIPCHK(c, clk.mark(1));
         hipLaunchKernelGGL(k_inflate_tab_window, dim3(1), dim3(1024), 0, st, item, d_ents, d_recs, d_lim);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, mark(2));
+        HIPCHK(c, clk.mark(2));
         if (stored) {
             hipLaunchKernelGGL(k_inflate_tab_resolve, dim3(cdiv(stored, 256 * it::RESOLVE_RUN)), dim3(256), 0, st, item, d_ents, d_lim, d_out);
             HIPCHK(c, hipGetLastError());
         }
-        HIPCHK(c, mark(3));
+        HIPCHK(c, clk.mark(3));
         // the group's last window stays on the device as the window in front of the next group
         if (k1 < n_blocks) HIPCHK(c, hipMemcpyAsync(c->t_dev, c->t_dev + (size_t)n * it::WIN, it::WIN, hipMemcpyDeviceToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(ic::Rec) * n, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));  // the one wait of a group
-        lap(0, 1, 0), lap(1, 2, 1), lap(2, 3, 2);
+        clk.lap(0, 1, 0), clk.lap(1, 2, 1), clk.lap(2, 3, 2);
         if (!it::it_report(reinterpret_cast<const ic::Rec*>(c->v_host + rec_at), n, acc)) break;
     }
-    // the second half of a framed call, as in inflate_run: the checksum of the output against the trailer
+    // the second half of a framed call: the accumulated record goes up as the one record of inflate_run's framed_tail
     if (iw::iw_judged(acc, (uint32_t)wrapper, cap)) {
         if (acc.out_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;  // (what the checksum kernels take)
-        const uint64_t n = acc.out_len;
         const size_t rec_at = align_up(sizeof(IItem), 256);
         rc = verify_room(c, rec_at + sizeof(iw::Rec));
         if (rc) return rc;
-        if (wrapper == 2) {
-            rc = ensure_buf(c, &c->d_crc, &c->d_crc_cap, ((size_t)cdiv(n, CRC_CHUNK) + 2) * 4 + 512);
-            if (rc) return rc;
-        }
         *reinterpret_cast<IItem*>(c->v_host) = IItem{d_stream, stream_len, d_out, cap, c->d_sc, (uint32_t)wrapper, 0u};
         *reinterpret_cast<iw::Rec*>(c->v_host + rec_at) = acc;
         HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, rec_at + sizeof(iw::Rec), hipMemcpyHostToDevice, st));
-        HIPCHK(c, mark(0));
-        HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-        if (wrapper == 1) launch_adler(c, st, d_out, n);
-        if (wrapper == 2) launch_crc(c, st, d_out, n, reinterpret_cast<uint32_t*>(c->d_crc));
-        hipLaunchKernelGGL(k_inflate_trailer, dim3(1), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
-                           reinterpret_cast<iw::Rec*>(c->v_dev + rec_at), 1u);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, mark(1));
-        HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        lap(0, 1, 3);
+        rc = framed_tail(c, st, 1, rec_at, [&]() { return launch_sums_one(c, st, wrapper, d_out, acc.out_len); }, [&](int k) { return clk.mark(k); });
+        if (rc) return rc;
+        clk.lap(0, 1, 3);
         acc = *reinterpret_cast<const iw::Rec*>(c->v_host + rec_at);
     }
     rc = inflate_rc(iw::iw_report(acc, cap, *report, valid));
@@ -267,9 +236,9 @@ int mi355_inflate_tabled_device(mi355_deflate_ctx* c, const void* d_stream, size
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    if (const int rc = shard_refusal(c)) return rc;
     return inflate_tabled_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, blocks, n_blocks, total,
-                              reinterpret_cast<uint8_t*>(d_out), out_cap, out_len, report, st, &valid);
+                              reinterpret_cast<uint8_t*>(d_out), out_cap, out_len, report, call_stream(c, hip_stream), &valid);
 }
 
 // HIP-event milliseconds of the context's last tabled call per launch kind, summed over its groups: decode, windows, resolve,
@@ -280,7 +249,7 @@ int mi355_inflate_tabled_last_stages(mi355_deflate_ctx* c, float ms[4]) {
     return MI355_OK;
 }
 
-// host buffers: the stream goes into the context's staging with a plain copy, the bytes that hold data come back with one
+// host buffers: staged_call around the tabled worker
 int mi355_inflate_tabled(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, const mi355_block_info* blocks,
                          size_t n_blocks, uint8_t* out, size_t out_cap, size_t* out_len, mi355_inflate_report* report) {
     if (!blocks || !n_blocks) return mi355_inflate(c, stream, stream_len, wrapper, out, out_cap, out_len, report);
@@ -290,26 +259,9 @@ int mi355_inflate_tabled(mi355_deflate_ctx* c, const uint8_t* stream, size_t str
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
-    if (rc) return rc;
-    rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_cap + 64);
-    if (rc) return rc;
-    hipStream_t st = c->own_stream;
-    if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
-    uint64_t valid = 0;
-    rc = inflate_tabled_one(c, c->d_in, stream_len, wrapper, blocks, n_blocks, total, out_cap ? c->d_out : nullptr, out_cap, out_len, report, st,
-                            &valid);
-    if (rc != MI355_OK && rc != MI355_E_DATA && rc != MI355_E_OUT_TOO_SMALL) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
-        return rc;
-    }
-    if (valid) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)valid, hipMemcpyDeviceToHost));
-    return rc;
+    return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
+        return inflate_tabled_one(c, d_stream, stream_len, wrapper, blocks, n_blocks, total, d_out, out_cap, out_len, report, st, valid);
+    });
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 // this input?  k_verify decodes without writing a byte -- the expected output is the input -- one wave per entry: an entry is a
 // restart point of the block table of the encode (mi355_deflate_last_blocks), or the whole stream when there is no table; the
 // batched form has one entry per item.  What is valid is decided by inflate_check.h, text that tests/inflcheck/ builds for the
-// host; this file adds the wave's way of comparing bytes and the host driver.  DESIGN.md section 11.
+// host; this file adds the wave's way of comparing bytes and the host driver, whose shared steps are in decode_host.inc.  DESIGN.md
+// section 11.
 #include "inflate_check.h"
 
 namespace mi355 {
@@ -104,21 +105,6 @@ static_assert(MI355_VERIFY_OK == ic::V_OK && MI355_VERIFY_FRAME == ic::V_FRAME &
                   MI355_VERIFY_TABLE == ic::V_TABLE && MI355_VERIFY_TRUNCATED == ic::V_TRUNCATED && MI355_VERIFY_TRAILER == ic::V_TRAILER &&
                   MI355_VERIFY_CHECKSUM == ic::V_CHECKSUM,
               "inflate_check.h mirrors MI355_VERIFY_*");
-constexpr uint64_t VERIFY_MAX_IN = 0xFFFF0000ull;  // 4 GiB - 64 KiB: what one pass encodes
-
-// the device and the page-locked side of a verify call's descriptors and records
-int verify_room(mi355_deflate_ctx* c, size_t bytes) {
-    int rc = ensure_buf(c, &c->v_dev, &c->v_dev_cap, bytes);
-    if (rc) return rc;
-    if (bytes > c->v_host_cap) {
-        if (c->v_host) (void)hipHostFree(c->v_host);
-        c->v_host = nullptr;
-        c->v_host_cap = 0;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->v_host), bytes, 0));
-        c->v_host_cap = bytes;
-    }
-    return MI355_OK;
-}
 
 void verify_say(mi355_deflate_ctx* c, const mi355_verify_report& r, const char* what) {
     char buf[200];
@@ -127,17 +113,19 @@ void verify_say(mi355_deflate_ctx* c, const mi355_verify_report& r, const char* 
     c->err = buf;
 }
 
-// one stream, device resident: checksum launches, k_verify over the entries, one copy back, one wait
+// what both single entries refuse before any work, in this order; table_bad: a table's length without the table
+int verify_refusal(mi355_deflate_ctx* c, const void* stream, size_t stream_len, const void* in, size_t in_len, int wrapper, bool table_bad,
+                   const mi355_verify_report* report) {
+    if (!report || (!stream && stream_len) || (!in && in_len) || wrapper < 0 || wrapper > 2 || table_bad) return MI355_E_ARG;
+    if (in_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;
+    return shard_refusal(c);
+}
+
+// one stream, device resident, behind verify_refusal: checksum launches, k_verify over the entries, one copy back, one wait
 int verify_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, const uint8_t* d_in, size_t in_len, int wrapper,
                const mi355_block_info* blocks, size_t n_blocks, mi355_verify_report* report, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!report || (!d_stream && stream_len) || (!d_in && in_len) || wrapper < 0 || wrapper > 2 || (!blocks && n_blocks)) return MI355_E_ARG;
-    if (in_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    if (!blocks) n_blocks = 0;
+    if (!blocks && n_blocks) return MI355_E_ARG;  // (mi355_deflate_verify has always left this pair to here, behind its copies)
     uint64_t sum = 0;
     for (size_t k = 0; k < n_blocks; k++) {
         if (k && blocks[k].bit_start < blocks[k - 1].bit_start) {
@@ -160,17 +148,14 @@ int verify_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len,
     const size_t bytes = rec_at + sizeof(ic::Rec) * ne;
     int rc = verify_room(c, bytes);
     if (rc) return rc;
-    if (wrapper == 2) {
-        rc = ensure_buf(c, &c->d_crc, &c->d_crc_cap, ((size_t)cdiv(in_len, CRC_CHUNK) + 2) * 4 + 512);
-        if (rc) return rc;
-    }
     VItem* hit = reinterpret_cast<VItem*>(c->v_host);
     *hit = VItem{d_stream, stream_len, d_in, in_len, wrapper ? c->d_sc : nullptr, (uint32_t)wrapper, 0u};
     ic::Entry* hent = reinterpret_cast<ic::Entry*>(c->v_host + ent_at);
     ic::ic_make_entries([&](uint64_t k) { return blocks[k].bit_start; }, [&](uint64_t k) { return blocks[k].in_bytes; }, n_blocks, 0u, hent);
-    if (wrapper) HIPCHK(c, hipMemsetAsync(c->d_sc, 0, sizeof(DevScalars), st));
-    if (wrapper == 1) launch_adler(c, st, d_in, in_len);
-    if (wrapper == 2) launch_crc(c, st, d_in, in_len, reinterpret_cast<uint32_t*>(c->d_crc));
+    if (wrapper) {
+        rc = launch_sums_one(c, st, wrapper, d_in, in_len);
+        if (rc) return rc;
+    }
     HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, rec_at, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_verify, dim3((uint32_t)ne), dim3(64), 0, st, reinterpret_cast<const VItem*>(c->v_dev),
                        reinterpret_cast<const ic::Entry*>(c->v_dev + ent_at), reinterpret_cast<ic::Rec*>(c->v_dev + rec_at));
@@ -195,25 +180,22 @@ int mi355_deflate_verify_device(mi355_deflate_ctx* c, const void* d_stream, size
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    if (const int rc = verify_refusal(c, d_stream, stream_len, d_in, in_len, wrapper, !blocks && n_blocks, report)) return rc;
     return verify_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, reinterpret_cast<const uint8_t*>(d_in), in_len, wrapper,
-                      blocks, n_blocks, report, st);
+                      blocks, n_blocks, report, call_stream(c, hip_stream));
 }
 
-// host buffers: the stream and the input go into the context's staging with plain copies
+// host buffers: the stream and the input go into the context's staging with plain copies (two inputs and nothing to hand back: not
+// the shape of staged_call)
 int mi355_deflate_verify(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, const uint8_t* in, size_t in_len, int wrapper,
                          const mi355_block_info* blocks, size_t n_blocks, mi355_verify_report* report) {
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
-    if (!report || (!stream && stream_len) || (!in && in_len) || wrapper < 0 || wrapper > 2) return MI355_E_ARG;
-    if (in_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
+    int rc = verify_refusal(c, stream, stream_len, in, in_len, wrapper, false, report);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, in_len + 64);
+    rc = ensure_buf(c, &c->d_in, &c->d_in_cap, in_len + 64);
     if (rc) return rc;
     rc = ensure_buf(c, &c->d_out, &c->d_out_cap, stream_len + 64);
     if (rc) return rc;
@@ -232,59 +214,36 @@ int mi355_deflate_verify_batch_device(mi355_deflate_ctx* c, mi355_batch_item* it
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
     const auto t0 = std::chrono::steady_clock::now();
-    if ((!items && n_items) || wrapper < 0 || wrapper > 2 || n_items > 0x7fffffffull) return MI355_E_ARG;
     std::vector<uint32_t> act;
-    for (size_t i = 0; i < n_items; i++) {
-        if (items[i].status != MI355_OK) continue;  // skipped, left alone
-        if ((!items[i].in && items[i].in_len) || (!items[i].out && items[i].out_len)) return MI355_E_ARG;
-        if (items[i].in_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;
-        act.push_back((uint32_t)i);
-    }
-    if (c->live_shard) {
-        c->err = "the context holds a sharded encode";
-        return MI355_E_STATE;
-    }
-    if (act.empty()) return MI355_OK;
+    int rc = batch_active(c, items, n_items, wrapper, act, [](const mi355_batch_item& it) {
+        return !it.out && it.out_len ? MI355_E_ARG : it.in_len > VERIFY_MAX_IN ? MI355_E_UNSUPPORTED : MI355_OK;
+    });
+    if (rc || act.empty()) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : c->own_stream;
+    hipStream_t st = call_stream(c, hip_stream);
     const size_t k = act.size();
-    // [VItem k][Entry k][BatchItem k][running sums BS_N x (k + 1)] | [DevState k] | [Rec k]
-    const size_t ent_at = align_up(sizeof(VItem) * k, 256), bat_at = align_up(ent_at + sizeof(ic::Entry) * k, 256);
-    const size_t pre_at = bat_at + (wrapper ? sizeof(BatchItem) * k : 0);
-    const size_t st_at = align_up(pre_at + (wrapper ? sizeof(uint32_t) * BS_N * (k + 1) : 0), 256);
-    const size_t rec_at = align_up(st_at + (wrapper ? sizeof(DevState) * k : 0), 256);
-    int rc = verify_room(c, rec_at + sizeof(ic::Rec) * k);
+    // [VItem k][Entry k] and the checksum plan behind them
+    const size_t ent_at = align_up(sizeof(VItem) * k, 256);
+    const BatchSums plan(ent_at + sizeof(ic::Entry) * k, k, wrapper != 0, sizeof(ic::Rec));
+    const size_t rec_at = plan.rec_at;
+    rc = verify_room(c, plan.bytes);
     if (rc) return rc;
     VItem* hit = reinterpret_cast<VItem*>(c->v_host);
     ic::Entry* hent = reinterpret_cast<ic::Entry*>(c->v_host + ent_at);
-    BatchItem* hb = reinterpret_cast<BatchItem*>(c->v_host + bat_at);
-    uint32_t* hpre = reinterpret_cast<uint32_t*>(c->v_host + pre_at);
-    DevState* dst = reinterpret_cast<DevState*>(c->v_dev + st_at);
-    if (wrapper) memset(c->v_host + bat_at, 0, st_at - bat_at);
     for (size_t j = 0; j < k; j++) {
         const mi355_batch_item& it = items[act[j]];
         hit[j] = VItem{reinterpret_cast<const uint8_t*>(it.out), it.out_len, reinterpret_cast<const uint8_t*>(it.in), it.in_len,
-                       wrapper ? &dst[j].sc : nullptr, (uint32_t)wrapper, 0u};
+                       wrapper ? &plan.states(c)[j].sc : nullptr, (uint32_t)wrapper, 0u};
         hent[j] = ic::Entry{0, 0, 0, 0, 1u, (uint32_t)j};
-        if (!wrapper) continue;
-        hb[j].in = hit[j].in;
-        hb[j].n = (uint32_t)it.in_len;
-        hb[j].st = dst + j;
-        const uint64_t wg[2] = {cdiv(it.in_len, ADLER_CHUNK), cdiv(it.in_len, 256 * CRC_CHUNK)};
-        for (uint32_t s = 0; s < 2; s++) {
-            const size_t row = (size_t)(s ? BS_CRC : BS_ADLER) * (k + 1);
-            const uint64_t t = (uint64_t)hpre[row + j] + wg[s];
-            if (t > 0x7fffffffull) return MI355_E_ARG;
-            hpre[row + j + 1] = (uint32_t)t;
-        }
     }
-    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, st_at, hipMemcpyHostToDevice, st));
     if (wrapper) {
-        HIPCHK(c, hipMemsetAsync(dst, 0, sizeof(DevState) * k, st));
-        const BatchArgs a{reinterpret_cast<const BatchItem*>(c->v_dev + bat_at), reinterpret_cast<const uint32_t*>(c->v_dev + pre_at), (uint32_t)k};
-        const uint32_t grid = hpre[(size_t)(wrapper == 1 ? BS_ADLER : BS_CRC) * (k + 1) + k];
-        if (grid && wrapper == 1) hipLaunchKernelGGL(kb_adler_part, dim3(grid), dim3(256), 0, st, a);
-        if (grid && wrapper == 2) hipLaunchKernelGGL(kb_crc, dim3(grid), dim3(256), 0, st, a);
+        rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* n) { *p = hit[j].in, *n = hit[j].in_len; });
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, plan.st_at, hipMemcpyHostToDevice, st));  // (the descriptors and the plan in one)
+    if (wrapper) {
+        rc = plan.launch(c, wrapper, st);
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(k_verify, dim3((uint32_t)k), dim3(64), 0, st, reinterpret_cast<const VItem*>(c->v_dev),
                        reinterpret_cast<const ic::Entry*>(c->v_dev + ent_at), reinterpret_cast<ic::Rec*>(c->v_dev + rec_at));
@@ -293,21 +252,13 @@ int mi355_deflate_verify_batch_device(mi355_deflate_ctx* c, mi355_batch_item* it
     HIPCHK(c, hipStreamSynchronize(st));
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     const ic::Rec* recs = reinterpret_cast<const ic::Rec*>(c->v_host + rec_at);
-    int first = MI355_OK;
-    for (size_t j = 0; j < k; j++) {
-        mi355_verify_report r;
-        ic::ic_report(recs + j, 1, r);
-        r.ms = ms;
-        if (reports) reports[act[j]] = r;
-        items[act[j]].status = r.status == MI355_VERIFY_OK ? MI355_OK : MI355_E_VERIFY;
-        if (r.status != MI355_VERIFY_OK && first == MI355_OK) {
-            first = MI355_E_VERIFY;
-            char what[48];
-            snprintf(what, sizeof what, "verify: item %u", act[j]);
-            verify_say(c, r, what);
-        }
-    }
-    return first;
+    return batch_give(
+        items, act, reports, ms, "verify",
+        [&](size_t j, mi355_batch_item&, mi355_verify_report& r) {
+            ic::ic_report(recs + j, 1, r);
+            return r.status == MI355_VERIFY_OK ? MI355_OK : MI355_E_VERIFY;
+        },
+        [&](const mi355_verify_report& r, int, const char* what) { verify_say(c, r, what); });
 }
 
 }  // extern "C"
