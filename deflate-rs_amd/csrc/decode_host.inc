@@ -101,10 +101,11 @@ struct BatchSums {
 };
 
 // HIP-event time between the launches of a call, only when asked (MI355_CFG_STAGE_CLOCKS): an event is idle queue between two
-// kernels.  The events, their flag and the milliseconds are the context's; N of each.
-template <int N>
+// kernels.  The events, their flag and the milliseconds are the context's: N slots of milliseconds, E events (N, unless the caller
+// brackets every launch with the same pair and laps it into the launch kind's slot).
+template <int N, int E = N>
 struct StageClocks {
-    hipEvent_t (&ev)[N];
+    hipEvent_t (&ev)[E];
     bool& ev_ok;
     float (&ms)[N];
     hipStream_t st;
@@ -113,14 +114,14 @@ struct StageClocks {
     int begin(mi355_deflate_ctx* c) {
         for (int k = 0; k < N; k++) ms[k] = 0;
         if (!on || ev_ok) return MI355_OK;
-        hipEvent_t made[N];
-        for (int k = 0; k < N; k++) {
+        hipEvent_t made[E];
+        for (int k = 0; k < E; k++) {
             const hipError_t e = hipEventCreate(&made[k]);
             if (e == hipSuccess) continue;
             for (int j = 0; j < k; j++) (void)hipEventDestroy(made[j]);
             HIPCHK(c, e);
         }
-        for (int k = 0; k < N; k++) ev[k] = made[k];
+        for (int k = 0; k < E; k++) ev[k] = made[k];
         ev_ok = true;
         return MI355_OK;
     }

@@ -244,6 +244,17 @@ struct mi355_deflate_ctx {
     bool x_ev_ok = false;
     float x_ms[3] = {};           // mi355_inflate_index_last_stages: find, walk, host link
     std::vector<uint8_t> x_walks; // mi355_inflate_index_last_walks: the last index's records, 80 bytes a span
+    // deflate_members_inflate.inc: the members of a gzip file
+    uint64_t member_span = 65536;  // MI355_CFG_INFLATE_MEMBER_SPAN_BYTES: compressed bytes of one span (im::SPAN_DEFAULT)
+    uint8_t* m_dev = nullptr;      // the candidates, the walkers' records and the chain's walkers of a call
+    size_t m_dev_cap = 0;
+    uint8_t* m_rows = nullptr;     // the rows of a fill, or the rows and records of a chain launch
+    size_t m_rows_cap = 0;
+    hipEvent_t m_ev[2] = {};       // around a launch of a members call, when the stage clocks are on
+    bool m_ev_ok = false;
+    float m_ms[6] = {};            // mi355_inflate_members_last_stages: find, walk, fill, member decode, chain decode, checksums
+    std::vector<uint64_t> m_cands; // mi355_inflate_members_last_walks: the last call's candidates and the records of its first
+    std::vector<uint8_t> m_walks;  // walk, 40 bytes a span
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1735,6 +1746,10 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
         for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->t_ev[k]);
     if (c->x_ev_ok)
         for (int k = 0; k < 3; k++) (void)hipEventDestroy(c->x_ev[k]);
+    if (c->m_dev) (void)hipFree(c->m_dev);
+    if (c->m_rows) (void)hipFree(c->m_rows);
+    if (c->m_ev_ok)
+        for (int k = 0; k < 2; k++) (void)hipEventDestroy(c->m_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

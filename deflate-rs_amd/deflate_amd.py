@@ -168,6 +168,26 @@ class IndexWalk(C.Structure):
                 ("in_pos", C.c_uint64)]
 
 
+MEMBER_HINTED = 1  # MI355_MEMBER_HINTED
+
+
+class MemberInfo(C.Structure):
+    """mi355_member_info (40 bytes): one member of a gzip file, as mi355_inflate_members walked it"""
+    _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("out_off", C.c_uint64), ("out_len", C.c_uint64),
+                ("flags", C.c_uint32), ("status", C.c_uint32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in MemberInfo._fields_}
+        d["status"] = VERIFY_STATUS[self.status] if self.status < len(VERIFY_STATUS) else self.status
+        return d
+
+
+class MemberWalk(C.Structure):
+    """mi355_member_walk (40 bytes): what the walker of one span of mi355_inflate_members left on its first walk"""
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("n_members", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("how", C.c_uint32), ("link", C.c_uint32)]
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -300,6 +320,12 @@ def load():
     L.mi355_inflate_parallel.argtypes = L.mi355_inflate.argtypes
     L.mi355_inflate_index_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mi355_inflate_index_last_walks.argtypes = [C.c_void_p, C.POINTER(IndexWalk), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_inflate_members_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_members.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport)]
+    L.mi355_inflate_members_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_inflate_members_last_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(MemberWalk), C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -330,6 +356,8 @@ EXPORTED = [
     "mi355_inflate_tabled", "mi355_inflate_tabled_device", "mi355_inflate_tabled_last_stages",
     "mi355_inflate_index", "mi355_inflate_index_device", "mi355_inflate_parallel", "mi355_inflate_parallel_device",
     "mi355_inflate_index_last_stages", "mi355_inflate_index_last_walks",
+    "mi355_inflate_members", "mi355_inflate_members_device", "mi355_inflate_members_last_stages",
+    "mi355_inflate_members_last_walks",
 ]
 
 
@@ -364,6 +392,7 @@ class Context:
     CFG_HOST_BOUNCE, CFG_HOST_THREADS, CFG_STAGE_CLOCKS, CFG_BATCH_BYTES = 7, 8, 9, 10
     CFG_INFLATE_GROUP_BYTES = 11
     CFG_INFLATE_INDEX_SPAN_BYTES = 12
+    CFG_INFLATE_MEMBER_SPAN_BYTES = 13
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -826,6 +855,87 @@ class Context:
             self._err(rc)
         return [tuple(getattr(a, f) for f, _t in IndexWalk._fields_) for a in arr[: n.value]]
 
+    # ---- a gzip file of any number of members (mi355_inflate_members*) ----
+    def _members(self, call, room, table=True):
+        """the call with a table of `room` entries, again with the count it names if that was too few (table False: whatever fits)"""
+        n, nm, r = C.c_size_t(0), C.c_size_t(0), InflateReport()
+        arr = (MemberInfo * max(room, 1))()
+        rc = call(arr, room, C.byref(n), C.byref(nm), C.byref(r))
+        if table and rc in (OK, E_DATA, E_OUT_TOO_SMALL) and nm.value > room:
+            room = nm.value
+            arr = (MemberInfo * room)()
+            rc = call(arr, room, C.byref(n), C.byref(nm), C.byref(r))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL):
+            self._err(rc)
+        return rc, n.value, r.as_dict(), [arr[k].as_dict() for k in range(min(nm.value, room))]
+
+    def inflate_members_raw(self, stream, out_cap=0, room=None):
+        """mi355_inflate_members on host bytes, nothing raised for the three outcomes of a decode: (rc, out_len, report dict, member
+        dicts, the bytes of the buffer that hold data).  out_cap 0 hands over no buffer (the size query).  room: entries of the
+        member table handed over -- None: a guess from the file's length, and the call again if the file has more; a number: that
+        many and no second call, the list is cut there (0: no table at all)."""
+        stream = bytes(stream)
+        out = (C.c_uint8 * out_cap)() if out_cap else None
+        rc, n, rep, members = self._members(
+            lambda arr, room, pn, pm, pr: load().mi355_inflate_members(self._h, stream, len(stream), C.cast(out, C.c_void_p) if out_cap else None,
+                                                                       out_cap, pn, arr if room else None, room, pm, pr),
+            max(64, len(stream) // 4096) if room is None else room, room is None)
+        held = min(n, out_cap)
+        return rc, n, rep, members, bytes(memoryview(out)[:held]) if held else b""
+
+    def _members_count(self, stream):
+        """(rc, out_len, members walked) of the size query: no buffer and no table"""
+        stream = bytes(stream)
+        n, nm, r = C.c_size_t(0), C.c_size_t(0), InflateReport()
+        rc = load().mi355_inflate_members(self._h, stream, len(stream), None, 0, C.byref(n), None, 0, C.byref(nm), C.byref(r))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL):
+            self._err(rc)
+        return rc, n.value, nm.value
+
+    def inflate_members(self, stream, out_cap=None):
+        """A gzip file of any number of members (BGZF, `cat a.gz b.gz`, a packed gzip arena) in host bytes -> (data, members).
+        out_cap None: the size is queried first.  Raises DeflateError(E_DATA, ...) for a file that is not valid and
+        DeflateError(E_OUT_TOO_SMALL, ...) for one longer than a given out_cap."""
+        room = None
+        if out_cap is None:  # the size query needs no table, and its member count is the room of the decode: two decodes in all
+            rc, out_cap, room = self._members_count(stream)
+            if rc == E_DATA:
+                self._err(rc)
+        rc, _n, _rep, members, data = self.inflate_members_raw(stream, out_cap, room)
+        if rc != OK:
+            self._err(rc)
+        return data, members
+
+    def inflate_members_device(self, d_stream_ptr, stream_len, d_out_ptr, out_cap, stream=0, check=False):
+        """mi355_inflate_members_device: device pointers.  Returns (rc, out_len, report dict, member dicts); rc is OK, E_DATA or
+        E_OUT_TOO_SMALL.  Other return codes raise, and so do those two with check=True."""
+        rc, n, rep, members = self._members(
+            lambda arr, room, pn, pm, pr: load().mi355_inflate_members_device(self._h, C.c_void_p(d_stream_ptr), stream_len, C.c_void_p(d_out_ptr),
+                                                                              out_cap, pn, arr, room, pm, pr, C.c_void_p(stream)),
+            max(64, stream_len // 16384))
+        if rc != OK and check:
+            self._err(rc)
+        return rc, n, rep, members
+
+    def inflate_members_stages(self):
+        """mi355_inflate_members_last_stages: HIP-event ms of the last members call per launch kind (zeros without CFG_STAGE_CLOCKS)"""
+        ms = (C.c_float * 6)()
+        rc = load().mi355_inflate_members_last_stages(self._h, ms)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("find_ms", "walk_ms", "fill_ms", "member_decode_ms", "chain_decode_ms", "checksums_ms"), ms))
+
+    def inflate_members_walks(self):
+        """mi355_inflate_members_last_walks: (candidates, walkers' records as tuples in MemberWalk's field order) of the find and
+        the first walk of the last members call, one of each per span; two empty lists behind an empty file"""
+        n = C.c_size_t(0)
+        load().mi355_inflate_members_last_walks(self._h, None, None, 0, C.byref(n))
+        cand, arr = (C.c_uint64 * max(n.value, 1))(), (MemberWalk * max(n.value, 1))()
+        rc = load().mi355_inflate_members_last_walks(self._h, cand, arr, n.value, C.byref(n))
+        if rc != OK:
+            self._err(rc)
+        return list(cand[: n.value]), [tuple(getattr(a, f) for f, _t in MemberWalk._fields_) for a in arr[: n.value]]
+
     def inflate_batch_device(self, items, wrapper=0, stream=0):
         """mi355_inflate_batch_device.  items: a BatchItem array (in_ / in_len the stream, out / out_cap the buffer, e.g. the out
         pointers of a packed arena moved to in_), or a list of (stream pointer, stream length, buffer pointer, buffer size) with an
@@ -899,10 +1009,15 @@ class InflateReports(list):
     items = None
 
 
-def inflate_bytes(stream, wrapper=0, ctx=None, blocks=None, parallel=False):
+def inflate_bytes(stream, wrapper=0, ctx=None, blocks=None, parallel=False, members=False):
     """The bytes `stream` (raw / zlib / gzip by wrapper) inflates to, decoded on the GPU; DeflateError(E_DATA, ...) if it is not valid.
     blocks: the block table of the encode that made the stream, for a parallel decode (Context.inflate); parallel: a parallel decode
-    of a stream from anywhere, the table found on the device."""
+    of a stream from anywhere, the table found on the device.  members: the stream is a gzip FILE of any number of members
+    (Context.inflate_members); wrapper 2 only, and neither blocks nor parallel."""
+    if members:
+        if wrapper != 2 or blocks is not None or parallel:
+            raise ValueError("members=True takes a gzip file: wrapper=2, and neither blocks nor parallel")
+        return (ctx or default_context()).inflate_members(stream)[0]
     return (ctx or default_context()).inflate(stream, wrapper, blocks=blocks, parallel=parallel)
 
 

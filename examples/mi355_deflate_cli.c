@@ -2,13 +2,15 @@
  * binds): compresses a file on the GPU, or with -d decompresses one.
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
  *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
+ *   mi355_deflate_cli -d --members [-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
  * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
  * -d / --decompress inflates IN (a raw, zlib or gzip stream by the format switch) to OUT on the GPU: mi355_inflate once without a
  * buffer for the size, once more for the bytes; exits with status 3 and the report if the stream is not valid.  With --parallel the
  * two calls are mi355_inflate_parallel: the block table of the stream is found on the GPU and every entry decoded by a wave of its own
- * (the way for one large file from anywhere); the result is the same.
+ * (the way for one large file from anywhere); the result is the same.  With --members IN is a gzip FILE of any number of members --
+ * BGZF, `cat a.gz b.gz` -- and the two calls are mi355_inflate_members (plain -d -gzip takes exactly one member); --members with -raw or -zlib is refused with the usage text.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
  *             -Wl,-rpath,$PWD/deflate-rs_amd -o /tmp/mi355_deflate_cli */
 #include <stdio.h>
@@ -25,24 +27,26 @@ static int fail(const char* what, int rc, mi355_deflate_ctx* ctx) {
 int main(int argc, char** argv) {
     int wrapper = 0, level = 1;
     size_t chunk = 0;
-    int verify = 0, decompress = 0, parallel = 0;
+    int verify = 0, decompress = 0, parallel = 0, members = 0, format_given = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
-        if (!strcmp(argv[a], "-raw")) wrapper = 0;
-        else if (!strcmp(argv[a], "-zlib")) wrapper = 1;
-        else if (!strcmp(argv[a], "-gzip")) wrapper = 2;
+        if (!strcmp(argv[a], "-raw")) wrapper = 0, format_given = 1;
+        else if (!strcmp(argv[a], "-zlib")) wrapper = 1, format_given = 1;
+        else if (!strcmp(argv[a], "-gzip")) wrapper = 2, format_given = 1;
         else if (!strcmp(argv[a], "-fast")) level = 0;
         else if (!strcmp(argv[a], "-default")) level = 1;
         else if (!strcmp(argv[a], "-best")) level = 2;
         else if (!strcmp(argv[a], "--verify") || !strcmp(argv[a], "-verify")) verify = 1;
         else if (!strcmp(argv[a], "-d") || !strcmp(argv[a], "--decompress")) decompress = 1;
         else if (!strcmp(argv[a], "--parallel") || !strcmp(argv[a], "-parallel")) parallel = 1;
+        else if (!strcmp(argv[a], "--members") || !strcmp(argv[a], "-members")) members = 1;
         else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
-    if (argc - a != 2 || (parallel && !decompress)) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n",
-                argv[0], argv[0]);
+    /* --members is gzip by definition: another format switch beside it is refused, not ignored */
+    if (argc - a != 2 || ((parallel || members) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2)) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n",
+                argv[0], argv[0], argv[0]);
         return 2;
     }
     FILE* f = fopen(argv[a], "rb");
@@ -57,6 +61,32 @@ int main(int argc, char** argv) {
     mi355_deflate_ctx* ctx = NULL;
     int rc = mi355_deflate_ctx_create(0, &ctx);
     if (rc) return fail("mi355_deflate_ctx_create (no GPU? there is no CPU fallback)", rc, NULL);
+    if (decompress && members) { /* a gzip file of any number of members: the size first, then the bytes */
+        mi355_inflate_report r;
+        size_t need = 0, got = 0, n_members = 0;
+        uint8_t* data = NULL;
+        rc = mi355_inflate_members(ctx, in, n, NULL, 0, &need, NULL, 0, &n_members, &r);
+        if (rc == MI355_E_OUT_TOO_SMALL) {
+            data = (uint8_t*)malloc(need);
+            if (!data) return fail("malloc", -1, NULL);
+            rc = mi355_inflate_members(ctx, in, n, data, need, &got, NULL, 0, &n_members, &r);
+        }
+        if (rc == MI355_E_DATA) {
+            fprintf(stderr, "inflate: member %lu: status %u at bit %llu, output byte %llu\n%s\n", (unsigned long)(n_members - 1), r.status,
+                    (unsigned long long)r.bit, (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
+            return 3;
+        }
+        if (rc) return fail("mi355_inflate_members", rc, ctx);
+        f = fopen(argv[a + 1], "wb");
+        if (!f || fwrite(data, 1, got, f) != got) return fail("write output", -1, NULL);
+        fclose(f);
+        fprintf(stderr, "%lu -> %lu bytes, %lu members, %llu blocks (%u stored, %u fixed, %u dynamic), %.3f ms\n", (unsigned long)n,
+                (unsigned long)got, (unsigned long)n_members, (unsigned long long)r.n_blocks, r.n_stored, r.n_fixed, r.n_dynamic, r.ms);
+        free(data);
+        free(in);
+        mi355_deflate_ctx_destroy(ctx);
+        return 0;
+    }
     if (decompress) { /* the size first (no buffer: the decode counts), then the bytes */
         mi355_inflate_report r;
         size_t need = 0, got = 0;

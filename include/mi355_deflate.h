@@ -165,7 +165,11 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *                          (default 16 KiB; 256 bytes .. 1 GiB): one wave searches a span for a block start and one walks on from
  *                          it, so a table has one entry per span at most.  Same bytes either way.  The default is the best of a
  *                          sweep over 16 / 32 / 64 / 128 KiB on 100 MB of text deflated by zlib at level 6: 55.5 / 70.4 / 83.1 /
- *                          140.1 ms for the whole mi355_inflate_parallel_device call (profiles/inflate_index_bench.json). */
+ *                          140.1 ms for the whole mi355_inflate_parallel_device call (profiles/inflate_index_bench.json).
+ *   MI355_CFG_INFLATE_MEMBER_SPAN_BYTES  compressed bytes of one span of mi355_inflate_members[_device] (default 64 KiB; 16 bytes ..
+ *                          1 GiB): one wave searches a span for a member that states its own size and one lane hops on from it.
+ *                          Same results either way.  The default is derived, not measured: a BGZF member is 64 KiB at most, so at
+ *                          that size every interior span of a BGZF file holds a member start. */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -178,6 +182,7 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_BATCH_BYTES 10
 #define MI355_CFG_INFLATE_GROUP_BYTES 11
 #define MI355_CFG_INFLATE_INDEX_SPAN_BYTES 12
+#define MI355_CFG_INFLATE_MEMBER_SPAN_BYTES 13
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
@@ -440,8 +445,8 @@ int mi355_deflate_verify_batch_device(mi355_deflate_ctx* ctx, mi355_batch_item* 
  * regions of a packed arena -- is decoded where it lies.  No reference item: the reference has no decoder.  Streams made by anyone
  * are accepted, not only ones this library encoded; pointers of any alignment.
  * wrapper: 0 / 1 / 2 as in verify, and the framing rules are verify's: zlib with FDICT is MI355_VERIFY_FRAME; ONE gzip member
- *   only, bytes after the trailer are MI355_VERIFY_TRAILER (so are bytes behind the BFINAL block of a raw stream); pad bits
- *   are ignored, as zlib does; a dynamic header is judged by zlib's rules (see verify).  Anything else is MI355_E_ARG.
+ *   only (a file of several: mi355_inflate_members below), bytes after the trailer are MI355_VERIFY_TRAILER (so are bytes behind
+ *   the BFINAL block of a raw stream); pad bits are ignored, as zlib does; a dynamic header is judged by zlib's rules (see verify).  Anything else is MI355_E_ARG.
  * Return value, for one stream and for each item of a batch:
  *   MI355_OK               out[0, out_len) is the data; report.out_pos == report.out_len.
  *   MI355_E_DATA           the report names the first failure in stream order (status, bit, out_pos); out[0, min(out_pos, out_cap))
@@ -565,6 +570,78 @@ typedef struct {
 } mi355_index_walk; /* 80 bytes */
 int mi355_inflate_index_last_stages(mi355_deflate_ctx* ctx, float ms[3]);
 int mi355_inflate_index_last_walks(mi355_deflate_ctx* ctx, mi355_index_walk* out, size_t cap, size_t* n_spans);
+
+/* ---- members: a gzip FILE, any number of members, BGZF members in parallel ------------------------------------
+ * RFC 1952 defines a gzip file as a sequence of members; mi355_inflate (wrapper 2) takes exactly one.  These calls take the
+ * sequence: BGZF (bgzip: BAM, tabix-indexed VCF), `cat a.gz b.gz`, and an arena of mi355_deflate_encode_batch_packed_device with gzip
+ * members whose regions lie back to back (pad bytes between regions would be the next member's FRAME).  No reference item: the reference has no decoder.
+ * The contract is the SERIAL WALK, whatever path produced a result:
+ *     o = 0, p = 0, m = 0
+ *     do:  member m begins at byte o.  Its header is mi355_inflate's gzip header (same rules), parsed on stream[o, stream_len);
+ *          failure, or fewer than 18 bytes left: MI355_VERIFY_FRAME (bit 0, out_pos p).
+ *          Its deflate blocks run through the BFINAL block, by mi355_inflate's rules and statuses; `bit` is counted from the member's
+ *          first deflate bit, and a distance is limited by the bytes THIS member has produced.
+ *          The 8 trailer bytes follow the byte in which the BFINAL block ends: bits needed from the file's last 8 bytes on are
+ *          MI355_VERIFY_TRUNCATED.  CRC-32 and ISIZE are of this member's output alone: MI355_VERIFY_CHECKSUM.
+ *          o = end of trailer, p += the member's output, m += 1
+ *     while o < stream_len
+ *   An empty file is FRAME.  Bytes behind a member that do not begin another member are that next member's FRAME: there is no
+ *   special case for zero padding (Python and GNU gzip skip it; these calls stay strict, as mi355_inflate is about trailing bytes).
+ *   Empty members (BGZF's 28-byte end-of-file marker) are legal anywhere.
+ * Return value, over the whole file, as mi355_inflate's:
+ *   MI355_OK               the file decoded and fits.
+ *   MI355_E_DATA           the first failure in file order (a CHECKSUM failure of member j comes before a structural failure of a
+ *                          member k > j); report.out_pos = the bytes produced in front of the failing element over all members, *out_len
+ *                          = min(out_pos, out_cap), the leading bytes of out that hold data.  A member's checksum is judged when
+ *                          all of its output was stored (it ends at or below out_cap).  DIFFERENT from mi355_inflate: the bytes of
+ *                          out[*out_len, out_cap) are unspecified -- members behind the failure may have been written already.
+ *   MI355_E_OUT_TOO_SMALL  every member is structurally valid and the total is larger than out_cap: *out_len is the exact total,
+ *                          out[0, out_cap) holds the first out_cap bytes, no checksum or ISIZE is judged.  out == NULL with out_cap
+ *                          == 0 is the size query.
+ *   MI355_E_UNSUPPORTED    a member that inflates to more than 4 GiB - 64 KiB (the checksum kernels' limit).
+ *   In every outcome nothing at or beyond out_cap is ever stored.  MI355_E_ARG (decided before a context or the device is touched)
+ *   / _STATE / _HIP, ctx == NULL, _device and host pointers, hip_stream: as in the inflate family.
+ * members (HOST memory, may be NULL with members_cap 0): one entry per member walked; *n_members (may be NULL) = their count -- after
+ *   MI355_E_DATA the failing member's index + 1, that entry carrying the status, in_len 0 unless the failure is CHECKSUM, and in out_len
+ *   the bytes counted in front of the failure.  The table is cut at members_cap without an error; the count is still the full one.
+ * report: mi355_inflate_report; on success the block counts are the sums over the members; reserved stays 0.  For a file of ONE
+ *   member the return value, *out_len, every report field but ms, and the bytes equal mi355_inflate(..., wrapper 2, ...), with one
+ *   exception: bytes behind the trailer are the next member's FRAME here and TRAILER there.
+ * How: a member that states its own size -- FEXTRA with a subfield 'B','C' of length 2 holding BSIZE = size - 1, as BGZF's -- is
+ *   HINTED.  The file is cut into spans of MI355_CFG_INFLATE_MEMBER_SPAN_BYTES; a wave per span finds the first hinted offset in it,
+ *   a lane per span hops from header to header, the host links the hops into the run of members from the current position, and the run
+ *   is decoded by the batched one-wave inflate, member k at the sum of the ISIZEs in front of it.  A hint is a claim and never
+ *   trusted for a byte: the run is accepted up to the first member that is not both structurally clean and exactly ISIZE bytes
+ *   long, and from there one wave walks member after member, open ended, until a hinted header follows again (at most 8 such
+ *   returns a call, which bounds the launches an adversarial file can cost and changes no result).  A large plain member is
+ *   walked by one wave, as mi355_inflate walks it.  The checksums: one pass of the batch's checksum launches over the member table. */
+#define MI355_MEMBER_HINTED 1u   /* the member's size was taken from its BC subfield and found true */
+typedef struct {
+    uint64_t in_off, in_len;     /* the member in the file, header through trailer */
+    uint64_t out_off, out_len;   /* its data in the output */
+    uint32_t flags, status;      /* MI355_MEMBER_*; MI355_VERIFY_* of this member */
+} mi355_member_info;             /* 40 bytes */
+int mi355_inflate_members_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, void* d_out, size_t out_cap,
+                                 size_t* out_len, mi355_member_info* members, size_t members_cap, size_t* n_members,
+                                 mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_members(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, uint8_t* out, size_t out_cap, size_t* out_len,
+                          mi355_member_info* members, size_t members_cap, size_t* n_members, mi355_inflate_report* report);
+/* A measuring aid like mi355_inflate_index_last_stages: HIP-event milliseconds of the context's last members call per launch kind,
+ * summed over its launches -- find, walk, fill, member decode, chain decode, checksums; zeros unless the stage clocks were on. */
+int mi355_inflate_members_last_stages(mi355_deflate_ctx* ctx, float ms[6]);
+/* A measuring aid like mi355_inflate_index_last_walks and no part of the stable interface: what the find and the first walk of the
+ * context's last members call (the run from byte 0) left on the device, one of each per span of the file -- cand[k], the span's
+ * candidate (UINT64_MAX: none), and walks[k], its walker's record.  *n_spans = their count (0 behind an empty file or a call that
+ * failed in front of its walk); more than cap: MI355_E_OUT_TOO_SMALL and nothing is written. */
+typedef struct {
+    uint64_t start;      /* where the walker began: byte 0 in span 0, else the span's candidate; UINT64_MAX: none */
+    uint64_t end;        /* where it stopped */
+    uint64_t n_members;  /* members hopped over */
+    uint64_t out_bytes;  /* the sum of their ISIZEs */
+    uint32_t how;        /* 0 linked to span `link`, 1 the end of the file, 2 a byte that is not hinted, 3 no candidate */
+    uint32_t link;
+} mi355_member_walk; /* 40 bytes */
+int mi355_inflate_members_last_walks(mi355_deflate_ctx* ctx, uint64_t* cand, mi355_member_walk* walks, size_t cap, size_t* n_spans);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
