@@ -129,12 +129,15 @@ def read_header(br):
 _FIXED = None
 
 
-def decode(raw, strict=True):
+def decode(raw, strict=True, positions=False, start=0, blocks=0):
     """-> list of blocks: dict(btype, bfinal, bit_start, bit_end, toks=[(0, byte) | (length, distance)], ll_syms, d_syms
     and, for a dynamic block, cl_lens / ll_lens / d_lens).  strict=False: a stream that cannot be read ends with a block
-    that holds what was read of it and an 'error'."""
+    that holds what was read of it and an 'error'.  positions=True: a compressed block also gets tok_pos, the bit its
+    every token begins at with the end-of-block code's bit as the last entry (so tok_pos[0] is where the header ends), and
+    a stored block gets payload, the byte offset of its first payload byte.  start: the bit the first block to read begins
+    at; blocks: read no more than that many (0: up to the final one)."""
     global _FIXED
-    br = _Bits(raw)
+    br = _Bits(raw, start)
     out = []
     while True:
         blk = dict(btype=None, bfinal=0, bit_start=br.p, toks=[], ll_syms=[], d_syms=[])
@@ -147,6 +150,8 @@ def decode(raw, strict=True):
                 n = br.get(16)
                 br.get(16)
                 blk["stored"] = n
+                if positions:
+                    blk["payload"] = br.p >> 3
                 br.p += 8 * n
             elif bt in (1, 2):
                 if bt == 1:
@@ -160,7 +165,10 @@ def decode(raw, strict=True):
                         raise ValueError(h["error"])
                     lt, dt = _table(h["ll_lens"]), _table(h["d_lens"])
                 toks, lls, ds = blk["toks"], blk["ll_syms"], blk["d_syms"]
+                pos = blk.setdefault("tok_pos", []) if positions else None
                 while True:
+                    if positions:
+                        pos.append(br.p)
                     s = _sym(br, lt)
                     lls.append(s)
                     if s == 256:
@@ -182,7 +190,7 @@ def decode(raw, strict=True):
             blk["error"] = str(e)
             break
         blk["bit_end"] = br.p
-        if blk["bfinal"]:
+        if blk["bfinal"] or len(out) == blocks:
             break
     return out
 
