@@ -308,6 +308,21 @@ MI355_IC Fail ic_flush_lits(Tables& t, const uint8_t* in, uint64_t lit_p, uint64
     return ic_fail(V_OK, 0, 0);
 }
 
+// ---- a match token, from its length symbol s (257..285) to a checked (len, dist): the text of ic_match_token.inc, which the
+// three symbol loops include, as a function -- what the host test calls (tests/test_match_token_cases.py).  w: the bits from the
+// token's first on, avail: how many of them are inside the stream; `used` comes in as the bits of s's code and goes out as the bits
+// of the whole token.  Every failure is reported at (at, p).
+template <class P>
+MI355_IC Fail ic_match_token(const Tables& t, uint64_t w, uint32_t s, uint32_t& used, uint64_t avail, uint64_t at, uint64_t p,
+                             uint32_t& len_out, uint32_t& dist_out) {
+    Fail f = ic_fail(V_OK, 0, 0);
+    do {
+#include "ic_match_token.inc"
+        len_out = len, dist_out = dist;
+    } while (false);
+    return f;
+}
+
 // ---- the symbols of one Huffman block, up to and including its end-of-block code --------------------------------------
 // `limit`: the input offset no token of this entry may pass; `past`: the status of one that does (LENGTH / TABLE)
 template <class P>
@@ -357,43 +372,7 @@ MI355_IC Fail ic_huffman_block(Tables& t, Bits& b, const uint8_t* in, uint64_t& 
             f = ic_fail(V_CODE, at, p);
             break;
         }
-        // a length: 257..264 = 3..10, then four codes per extra bit, 285 = 258
-        const uint32_t lc = s - 257;
-        uint32_t len = 3 + lc, eb = 0;
-        if (lc == 28) {
-            len = 258;
-        } else if (lc >= 8) {
-            eb = (lc >> 2) - 1;
-            len = 3 + ((4 + (lc & 3)) << eb) + ((uint32_t)(w >> used) & ((1u << eb) - 1));
-        }
-        used += eb;
-        uint32_t dused;
-        const uint32_t ds = ic_decode<P>(t.prim_d, D_BITS, t.sym_d, 31, t.cnt_d, w >> used, dused);
-        if (ds == NOCODE) {
-            const uint64_t davail = used < avail ? avail - used : 0;
-            f = ic_fail(davail < 15 && ic_longer_code_exists(t.cnt_d, davail) ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        if (ds >= 30) {
-            f = ic_fail(used + dused > avail ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        used += dused;
-        // a distance: 0..3 = 1..4, then two codes per extra bit
-        uint32_t dist = 1 + ds, de = 0;
-        if (ds >= 4) {
-            de = (ds >> 1) - 1;
-            dist = 1 + ((2 + (ds & 1)) << de) + ((uint32_t)(w >> used) & ((1u << de) - 1));
-        }
-        used += de;  // (15 + 5 + 15 + 13 = 48 bits at most: inside the 57 of ic_peek)
-        if (used > avail) {
-            f = ic_fail(V_TRUNCATED, at, p);
-            break;
-        }
-        if (dist > 32768 || dist > p) {
-            f = ic_fail(V_DISTANCE, at, p);
-            break;
-        }
+#include "ic_match_token.inc"
         if (len > limit - p) {  // (p <= limit always)
             f = ic_fail(past, at, p);
             break;
@@ -413,16 +392,10 @@ MI355_IC Fail ic_huffman_block(Tables& t, Bits& b, const uint8_t* in, uint64_t& 
     return ic_fail(V_OK, 0, 0);
 }
 
-// one stored piece: pad to the byte, LEN, NLEN, LEN bytes
+// one stored piece: its header (pad to the byte, LEN, NLEN), LEN bytes
 template <class P>
 MI355_IC Fail ic_stored_block(Bits& b, const uint8_t* in, uint64_t& p, uint64_t limit, uint32_t past) {
-    b.pos = (b.pos + 7) & ~7ull;  // (the pad bits are ignored, as zlib's inflate does)
-    const uint64_t at = b.pos;
-    const uint32_t len = ic_take(b, 16), nlen = ic_take(b, 16);
-    if (b.over) return ic_fail(V_TRUNCATED, at, p);
-    if ((len ^ nlen) != 0xFFFFu) return ic_fail(V_STORED, at, p);
-    const uint64_t byte0 = b.pos >> 3;
-    if (len > b.nbytes - byte0) return ic_fail(V_TRUNCATED, at, p);  // (byte0 <= nbytes: not over)
+#include "ic_stored_header.inc"
     if (len > limit - p) return ic_fail(past, at, p);
     const uint64_t d = P::first_diff_run(b.s + byte0, in + p, len);
     if (d < len) return ic_fail(V_MISMATCH, at, p + d);

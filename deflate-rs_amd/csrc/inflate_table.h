@@ -9,11 +9,11 @@
 //               bytes and markers alike; a source in front of pos_e loads nothing, its marker is computed.
 //   2. windows  the resolved window W_e (real bytes) behind every entry from W_{e-1} and the entry's symbols: the one serial part.
 //   3. resolve  out[q] = sym[q] < 256 ? sym[q] : W_{e-1}[sym[q] - 256], flat over the output.
-// The bit reader, the tables, the header rules and the frame parsers are inflate_check.h's and the match's source index is
-// inflate_write.h's, unchanged; the symbol loop, the stored piece and the entry loop are SIBLINGS of theirs once more (their text,
-// reports and registers stay what they were), with verify's end-of-entry tests and inflate's sink.  Every entry must end exactly at
-// the next one's bit and output position -- anything else is TABLE --, so a table that passes describes the one serial walk of the
-// stream: a wrong table cannot yield wrong bytes with OK.
+// The bit reader, the tables, the header rules, the frame parsers, the match token (ic_match_token.inc) and the stored header
+// (ic_stored_header.inc) are inflate_check.h's and the match's source index is inflate_write.h's; the symbol loop, the stored piece and
+// the entry loop around them are SIBLINGS of theirs once more, with verify's end-of-entry tests and inflate's sink.  Every entry
+// must end exactly at the next one's bit and output position -- anything else is TABLE --, so a table that passes describes the one
+// serial walk of the stream: a wrong table cannot yield wrong bytes with OK.
 //
 // Safety, as in inflate_write.h: the stream is read through the bounded reader; a symbol is stored only at a position below the
 // entry's limit (a token that would pass it is TABLE before it stores) and below `cap`, and loaded only at a position in
@@ -136,43 +136,8 @@ MI355_IC Fail it_huffman_block(Tables& t, Bits& b, Sink& o, uint64_t& p, uint64_
             f = ic_fail(V_CODE, at, p);
             break;
         }
-        // a length: 257..264 = 3..10, then four codes per extra bit, 285 = 258
-        const uint32_t lc = s - 257;
-        uint32_t len = 3 + lc, eb = 0;
-        if (lc == 28) {
-            len = 258;
-        } else if (lc >= 8) {
-            eb = (lc >> 2) - 1;
-            len = 3 + ((4 + (lc & 3)) << eb) + ((uint32_t)(w >> used) & ((1u << eb) - 1));
-        }
-        used += eb;
-        uint32_t dused;
-        const uint32_t ds = ic_decode<P>(t.prim_d, D_BITS, t.sym_d, 31, t.cnt_d, w >> used, dused);
-        if (ds == NOCODE) {
-            const uint64_t davail = used < avail ? avail - used : 0;
-            f = ic_fail(davail < 15 && ic_longer_code_exists(t.cnt_d, davail) ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        if (ds >= 30) {
-            f = ic_fail(used + dused > avail ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        used += dused;
-        // a distance: 0..3 = 1..4, then two codes per extra bit
-        uint32_t dist = 1 + ds, de = 0;
-        if (ds >= 4) {
-            de = (ds >> 1) - 1;
-            dist = 1 + ((2 + (ds & 1)) << de) + ((uint32_t)(w >> used) & ((1u << de) - 1));
-        }
-        used += de;  // (48 bits at most: inside the 57 of ic_peek)
-        if (used > avail) {
-            f = ic_fail(V_TRUNCATED, at, p);
-            break;
-        }
-        if (dist > 32768 || dist > p) {  // (p is the position in the whole output: no marker points in front of the stream)
-            f = ic_fail(V_DISTANCE, at, p);
-            break;
-        }
+        // (p is the position in the whole output: DISTANCE where a marker would point in front of the stream)
+#include "ic_match_token.inc"
         if (len > limit - p) {  // (p <= limit always)
             f = ic_fail(V_TABLE, at, p);
             break;
@@ -200,13 +165,7 @@ MI355_IC Fail it_huffman_block(Tables& t, Bits& b, Sink& o, uint64_t& p, uint64_
 // one stored piece (sibling of iw_stored_block)
 template <class P>
 MI355_IC Fail it_stored_block(Bits& b, Sink& o, uint64_t& p, uint64_t limit) {
-    b.pos = (b.pos + 7) & ~7ull;  // (the pad bits are ignored, as zlib's inflate does)
-    const uint64_t at = b.pos;
-    const uint32_t len = ic_take(b, 16), nlen = ic_take(b, 16);
-    if (b.over) return ic_fail(V_TRUNCATED, at, p);
-    if ((len ^ nlen) != 0xFFFFu) return ic_fail(V_STORED, at, p);
-    const uint64_t byte0 = b.pos >> 3;
-    if (len > b.nbytes - byte0) return ic_fail(V_TRUNCATED, at, p);  // (byte0 <= nbytes: not over)
+#include "ic_stored_header.inc"
     if (len > limit - p) return ic_fail(V_TABLE, at, p);
     if (len && p < o.cap) P::copy_run(b.s + byte0, o, p, len);
     p += len;

@@ -1,11 +1,13 @@
 // inflate_write.h -- the write side of inflate_check.h: decode a raw / zlib / gzip deflate stream to its bytes.
 //
 // The inflate entry points (include/mi355_deflate.h mi355_inflate*) run this text: the kernel (deflate_inflate.inc k_inflate, one
-// wave per stream) and the host build of tests/inflwrite/.  The bit reader, the tables, the dynamic-header rules, the frame parsers
-// and the length / distance arithmetic are inflate_check.h's, unchanged; what is here is a SIBLING of its symbol loop, stored piece
-// and block loop in which a sink stands where verify has a compare: a literal, a match or a stored piece is written, and a match
-// reads what the same wave wrote a moment ago.  (A sibling and not one loop with two sinks: verify's text, and with it its reports
-// and its kernel's registers, stay exactly what they were.)  The policy `P` adds to verify's leader / sync / uni:
+// wave per stream) and the host build of tests/inflwrite/.  The bit reader, the tables, the dynamic-header rules and the frame
+// parsers are inflate_check.h's, and so is everything of a token and of a stored piece that has no sink in it: the text of
+// ic_match_token.inc (a length symbol to a checked (len, dist)) and of ic_stored_header.inc (pad, LEN, NLEN) is included here, not
+// written again.  What is here is a SIBLING of its symbol loop, stored piece and block loop in which a sink stands where verify has a
+// compare: a literal, a match or a stored piece is written, and a match reads what the same wave wrote a moment ago.  (Siblings
+// around the shared text and not one loop with two sinks: what verify does with a token, and with it its reports and its kernel's
+// code, stays what it was.)  The policy `P` adds to verify's leader / sync / uni:
 //   store_lits  the gathered literals, lane i writing byte lit_p + i
 //   copy_match  64 bytes a step; byte i of a match (len, dist) at p is out[p - dist + i % dist]: a source index below p whatever
 //               dist is, so no step of a match reads what an earlier step of it wrote and an overlapping match needs no serial loop
@@ -121,43 +123,7 @@ MI355_IC Fail iw_huffman_block(Tables& t, Bits& b, Sink& o, uint64_t& p) {
             f = ic_fail(V_CODE, at, p);
             break;
         }
-        // a length: 257..264 = 3..10, then four codes per extra bit, 285 = 258
-        const uint32_t lc = s - 257;
-        uint32_t len = 3 + lc, eb = 0;
-        if (lc == 28) {
-            len = 258;
-        } else if (lc >= 8) {
-            eb = (lc >> 2) - 1;
-            len = 3 + ((4 + (lc & 3)) << eb) + ((uint32_t)(w >> used) & ((1u << eb) - 1));
-        }
-        used += eb;
-        uint32_t dused;
-        const uint32_t ds = ic_decode<P>(t.prim_d, D_BITS, t.sym_d, 31, t.cnt_d, w >> used, dused);
-        if (ds == NOCODE) {
-            const uint64_t davail = used < avail ? avail - used : 0;
-            f = ic_fail(davail < 15 && ic_longer_code_exists(t.cnt_d, davail) ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        if (ds >= 30) {
-            f = ic_fail(used + dused > avail ? V_TRUNCATED : V_CODE, at, p);
-            break;
-        }
-        used += dused;
-        // a distance: 0..3 = 1..4, then two codes per extra bit
-        uint32_t dist = 1 + ds, de = 0;
-        if (ds >= 4) {
-            de = (ds >> 1) - 1;
-            dist = 1 + ((2 + (ds & 1)) << de) + ((uint32_t)(w >> used) & ((1u << de) - 1));
-        }
-        used += de;  // (48 bits at most: inside the 57 of ic_peek)
-        if (used > avail) {
-            f = ic_fail(V_TRUNCATED, at, p);
-            break;
-        }
-        if (dist > 32768 || dist > p) {
-            f = ic_fail(V_DISTANCE, at, p);
-            break;
-        }
+#include "ic_match_token.inc"
         iw_flush_lits<P>(t, o, lit_p, n_lit);  // the match may source from them
         if (p < o.cap) {
             // the bytes it loads: [p - dist, p - dist + min(len, dist)).  Stores behind the last fence are not loadable yet.
@@ -178,16 +144,10 @@ MI355_IC Fail iw_huffman_block(Tables& t, Bits& b, Sink& o, uint64_t& p) {
     return ic_fail(V_OK, 0, 0);
 }
 
-// one stored piece: pad to the byte, LEN, NLEN, LEN bytes (sibling of ic_stored_block)
+// one stored piece: its header, LEN bytes (sibling of ic_stored_block)
 template <class P>
 MI355_IC Fail iw_stored_block(Bits& b, Sink& o, uint64_t& p) {
-    b.pos = (b.pos + 7) & ~7ull;  // (the pad bits are ignored, as zlib's inflate does)
-    const uint64_t at = b.pos;
-    const uint32_t len = ic_take(b, 16), nlen = ic_take(b, 16);
-    if (b.over) return ic_fail(V_TRUNCATED, at, p);
-    if ((len ^ nlen) != 0xFFFFu) return ic_fail(V_STORED, at, p);
-    const uint64_t byte0 = b.pos >> 3;
-    if (len > b.nbytes - byte0) return ic_fail(V_TRUNCATED, at, p);  // (byte0 <= nbytes: not over)
+#include "ic_stored_header.inc"
     if (len && p < o.cap) P::copy_run(b.s + byte0, o.out, o.cap, p, len);
     p += len;
     b.pos += 8ull * len;

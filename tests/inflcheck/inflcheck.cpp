@@ -129,5 +129,17 @@ extern "C" int inflcheck_verify_lanes(const uint8_t* stream, uint64_t stream_len
     return verify_as(true, stream, stream_len, in, in_len, wrapper, bit_start, in_bytes, n, report);
 }
 
+// ic_match_token alone, under a distance set built from 32 code lengths: w holds the token's bits from the length symbol's code on,
+// `used` the bits of that code.  out: status, len, dist, used (len / dist / used mean something where the status is OK)
+extern "C" void inflcheck_match_token(const uint8_t* dist_lens32, uint64_t w, uint32_t s, uint32_t used, uint64_t avail, uint64_t p,
+                                      uint32_t out[4]) {
+    ic::Tables t;
+    memset(&t, 0, sizeof t);
+    (void)ic::ic_build(t, dist_lens32, 32, t.prim_d, ic::D_BITS, t.sym_d, 31, t.cnt_d);
+    uint32_t len = 0, dist = 0;
+    const ic::Fail f = ic::ic_match_token<HostOps>(t, w, s, used, avail, 0, p, len, dist);
+    out[0] = f.status, out[1] = len, out[2] = dist, out[3] = used;
+}
+
 extern "C" uint32_t inflcheck_report_size(void) { return (uint32_t)sizeof(mi355_verify_report); }
 extern "C" uint32_t inflcheck_tables_size(void) { return (uint32_t)sizeof(ic::Tables); }

@@ -33,6 +33,9 @@ def lib():
         L.inflcheck_verify.restype = C.c_int
         L.inflcheck_verify_lanes.argtypes = L.inflcheck_verify.argtypes
         L.inflcheck_verify_lanes.restype = C.c_int
+        L.inflcheck_match_token.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                            C.POINTER(C.c_uint32)]
+        L.inflcheck_match_token.restype = None
         L.inflcheck_report_size.restype = C.c_uint32
         L.inflcheck_tables_size.restype = C.c_uint32
         _lib = L
@@ -49,6 +52,15 @@ def verify(stream, data, wrapper=0, table=None, lanes=False):
     rc = (lib().inflcheck_verify_lanes if lanes else lib().inflcheck_verify)(bytes(stream), len(stream), bytes(data), len(data), wrapper, bs, ib, n, C.byref(r))
     return rc, dict(status=STATUS[r.status] if r.status < len(STATUS) else r.status, entry=r.entry, bit=r.bit, in_pos=r.in_pos,
                     n_blocks=r.n_blocks, n_stored=r.n_stored, n_fixed=r.n_fixed, n_dynamic=r.n_dynamic)
+
+
+def match_token(dist_lens, w, s, used, avail, p):
+    """ic_match_token under the distance set of the 32 code lengths `dist_lens`: w holds the token's bits from the length symbol's
+    code on (bit 0 first), used the bits of that code, avail the bits inside the stream.  Returns (status name, len, dist, used)."""
+    assert len(dist_lens) == 32
+    out = (C.c_uint32 * 4)()
+    lib().inflcheck_match_token(bytes(dist_lens), w, s, used, avail, p, out)
+    return STATUS[out[0]] if out[0] < len(STATUS) else out[0], out[1], out[2], out[3]
 
 
 def write_corpus(path, cases):
