@@ -255,6 +255,14 @@ struct mi355_deflate_ctx {
     float m_ms[6] = {};            // mi355_inflate_members_last_stages: find, walk, fill, member decode, chain decode, checksums
     std::vector<uint64_t> m_cands; // mi355_inflate_members_last_walks: the last call's candidates and the records of its first
     std::vector<uint8_t> m_walks;  // walk, 40 bytes a span
+    // deflate_bigmembers_inflate.inc: the large plain members of a gzip file
+    uint64_t member_parallel = 65536;  // MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES: bytes left for a discovery (ib::PAR_DEFAULT); 0: off
+    uint8_t* mp_dev = nullptr;         // the head, the carried window, the candidates and the walkers' records of a discovery
+    size_t mp_dev_cap = 0;
+    hipEvent_t mp_ev[4] = {};          // between the launches of a discovery round and of a group, when the stage clocks are on
+    bool mp_ev_ok = false;
+    float mp_ms[5] = {};               // mi355_inflate_members_last_parallel_stages: find, walk, decode, windows, resolve
+    uint64_t mp_stats[6] = {};         // mi355_inflate_members_last_parallel
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1748,8 +1756,11 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
         for (int k = 0; k < 3; k++) (void)hipEventDestroy(c->x_ev[k]);
     if (c->m_dev) (void)hipFree(c->m_dev);
     if (c->m_rows) (void)hipFree(c->m_rows);
+    if (c->mp_dev) (void)hipFree(c->mp_dev);
     if (c->m_ev_ok)
         for (int k = 0; k < 2; k++) (void)hipEventDestroy(c->m_ev[k]);
+    if (c->mp_ev_ok)
+        for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->mp_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

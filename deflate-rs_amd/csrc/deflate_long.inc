@@ -589,6 +589,7 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
     // (like the argument errors of the calls it tunes: decided before a context or the device is touched)
     if (key == MI355_CFG_INFLATE_INDEX_SPAN_BYTES && (value < 256 || value > (1ull << 30))) return MI355_E_ARG;
     if (key == MI355_CFG_INFLATE_MEMBER_SPAN_BYTES && (value < 16 || value > (1ull << 30))) return MI355_E_ARG;
+    if (key == MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES && value && (value < 1024 || value > (1ull << 30))) return MI355_E_ARG;
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
@@ -641,6 +642,9 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
         return MI355_OK;
     case MI355_CFG_INFLATE_MEMBER_SPAN_BYTES:
         c->member_span = value;
+        return MI355_OK;
+    case MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES:
+        c->member_parallel = value;
         return MI355_OK;
     case MI355_CFG_SORT_RANKS:
         if (value > 1) return MI355_E_ARG;

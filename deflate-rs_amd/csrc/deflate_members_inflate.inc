@@ -6,8 +6,9 @@
 //   k_member_fill    one lane per walker on the chain: the (offset, size, ISIZE) rows of its members
 //   k_inflate_chain  one workgroup of one wave: member after member, open ended (Path B)
 // The hinted members themselves are decoded by k_inflate as it stands, and the members' checksums by the batch plan and
-// k_inflate_trailer of deflate_inflate.inc.  Nothing waits inside a kernel.  The host driver's shared steps are in decode_host.inc.
-// DESIGN.md section 15.
+// k_inflate_trailer of deflate_inflate.inc.  A large member that states no size is found and decoded in parallel by the kernels of
+// deflate_bigmembers_inflate.inc, which MemberDev::chain drives (inflate_bigmembers.h).  Nothing waits inside a kernel.  The host
+// driver's shared steps are in decode_host.inc.  DESIGN.md section 15.
 #include "inflate_members.h"
 
 namespace mi355 {
@@ -51,12 +52,13 @@ struct ChainArgs {
     uint8_t* out;
     uint64_t out_cap;
     uint32_t ignore_hints, room;
+    uint32_t behind, pad;  // members the launch set has walked in front of o (inflate_bigmembers.h)
 };
 __global__ __launch_bounds__(64) void k_inflate_chain(const ChainArgs a, im::Member* __restrict__ rows, iw::Rec* __restrict__ recs,
                                                       im::ChainEnd* __restrict__ end) {
     __shared__ ic::Tables s_t;
     im::ChainEnd e;
-    im::im_chain<MemberOps>(s_t, a.s, a.n, a.o, a.p, a.out, a.out_cap, a.ignore_hints != 0, rows, recs, a.room, e);
+    im::im_chain_behind<MemberOps>(s_t, a.s, a.n, a.o, a.p, a.out, a.out_cap, a.ignore_hints != 0, a.behind, rows, recs, a.room, e);
     if (threadIdx.x == 0) *end = e;
 }
 
@@ -81,6 +83,8 @@ struct MemberDev {
     uint64_t out_cap, S, n_spans;
     hipStream_t st;
     StageClocks<6, 2>& clk;
+    StageClocks<5, 4>& pclk;  // the launch kinds of the large plain members: discovery find and walk, tabled decode, window chains, resolve
+    ib::Stats stats = {};
     uint64_t* d_cand = nullptr;
     im::Walk* d_walk = nullptr;
     im::Seg* d_seg = nullptr;
@@ -156,10 +160,107 @@ struct MemberDev {
         HIPCHK(c, hipMemcpyAsync(got.data(), c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
         return wait(3);
     }
+    // Path B from (o, p): by discovery and the joint tabled launch sets when enough of the file is left, else -- and for what those
+    // leave -- by the one wave
     int chain(uint64_t o, uint64_t p, bool ignore_hints, std::vector<im::Member>& rows, std::vector<iw::Rec>& got, im::ChainEnd& e) {
+        if (c->member_parallel && o < n && n - o >= c->member_parallel && ix::ix_n_spans(n, c->index_span) <= 0x7fffffffull)
+            return ib::ib_chain<ib::Rules>(*this, s, n, o, p, out, out_cap, ignore_hints, CHAIN_ROOM, rows, got, e, stats);
+        return serial(o, p, ignore_hints, 0u, CHAIN_ROOM, rows, got, e);
+    }
+    uint64_t threshold() const { return c->member_parallel; }
+    uint64_t span() const { return c->index_span; }
+    uint64_t group_bytes() const { return c->inflate_group_bytes; }
+    // the head of the member at o: the finder's workgroup of span 0 alone (its candidate is o's first deflate bit, whatever stands there)
+    int head(uint64_t o, ib::Head& h) {
+        const uint64_t n_all = ix::ix_n_spans(n, c->index_span);
+        const size_t cand_at = 256 + it::WIN, walk_at = align_up(cand_at + sizeof(uint64_t) * n_all, 256);
+        if (const int rc = ensure_buf(c, &c->mp_dev, &c->mp_dev_cap, walk_at + sizeof(ix::Walk) * n_all)) return rc;
+        const DItem d{s, n, o, c->index_span, 0, 1, 1, 1u, 0u};
+        HIPCHK(c, pclk.mark(0));
+        hipLaunchKernelGGL(k_bigmember_find, dim3(1), dim3(64), 0, st, d, reinterpret_cast<uint64_t*>(c->mp_dev + cand_at),
+                           reinterpret_cast<ib::Head*>(c->mp_dev));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, pclk.mark(1));
+        HIPCHK(c, hipMemcpyAsync(&h, c->mp_dev, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        pclk.lap(0, 1, 0);
+        return MI355_OK;
+    }
+    // one round of a discovery (ib_discover): [Head] | [carried window] | [candidate n_all] | [Walk n_all], sized once for the file
+    int round(uint64_t o, bool first, uint64_t rewalk, uint64_t k_lo, uint64_t k_hi, ib::Head& head, std::vector<ix::Walk>& w) {
+        const uint64_t n_all = ix::ix_n_spans(n, c->index_span);
+        if (k_hi > n_all || k_lo > k_hi || rewalk >= k_hi || w.size() < k_hi) return MI355_E_HIP;  // (never)
+        const size_t cand_at = 256 + it::WIN, walk_at = align_up(cand_at + sizeof(uint64_t) * n_all, 256);
+        if (const int rc = ensure_buf(c, &c->mp_dev, &c->mp_dev_cap, walk_at + sizeof(ix::Walk) * n_all)) return rc;
+        ib::Head* d_head = reinterpret_cast<ib::Head*>(c->mp_dev);
+        uint64_t* d_c = reinterpret_cast<uint64_t*>(c->mp_dev + cand_at);
+        ix::Walk* d_w = reinterpret_cast<ix::Walk*>(c->mp_dev + walk_at);
+        const DItem d{s, n, o, c->index_span, rewalk, k_lo, k_hi, first ? 1u : 0u, 0u};
+        const uint64_t n_find = first ? k_hi : k_hi - k_lo;
+        HIPCHK(c, pclk.mark(0));
+        if (n_find) hipLaunchKernelGGL(k_bigmember_find, dim3((uint32_t)n_find), dim3(64), 0, st, d, d_c, d_head);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, pclk.mark(1));
+        hipLaunchKernelGGL(k_bigmember_walk, dim3((uint32_t)(k_hi - k_lo + 1)), dim3(64), 0, st, d, d_c, d_w);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, pclk.mark(2));
+        if (first) HIPCHK(c, hipMemcpyAsync(&head, d_head, sizeof head, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(w.data() + rewalk, d_w + rewalk, sizeof(ix::Walk), hipMemcpyDeviceToHost, st));
+        if (k_hi > k_lo) HIPCHK(c, hipMemcpyAsync(w.data() + k_lo, d_w + k_lo, sizeof(ix::Walk) * (k_hi - k_lo), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        pclk.lap(0, 1, 0), pclk.lap(1, 2, 1);
+        return MI355_OK;
+    }
+    // the three passes over one group of parts: descriptors [Entry n] | [Part np] | [limit np] | [Rec n], workspace [window n + 1]
+    // [symbols]; the window a group leaves for the next one waits in the discovery room (the workspace may move when it grows)
+    int decode(const ib::Plan& g, bool first, std::vector<ic::Rec>& got) {
+        const size_t k = g.ents.size(), np = g.parts.size();
+        got.resize(k);
+        if (!k || !np || k > it::GROUP_ENTRIES) return MI355_E_HIP;  // (never)
+        const size_t parts_at = align_up(sizeof(ic::Entry) * k, 256), lim_at = align_up(parts_at + sizeof(ib::Part) * np, 256);
+        const size_t rec_at = align_up(lim_at + sizeof(uint64_t) * np, 256), sym_at = (k + 1) * it::WIN;
+        if (const int rc = verify_room(c, rec_at + sizeof(ic::Rec) * k)) return rc;
+        if (const int rc = ensure_buf(c, &c->t_dev, &c->t_dev_cap, sym_at + 2 * (size_t)g.syms + 256)) return rc;
+        if (const int rc = ensure_buf(c, &c->mp_dev, &c->mp_dev_cap, 256 + it::WIN)) return rc;
+        memcpy(c->v_host, g.ents.data(), sizeof(ic::Entry) * k);
+        memcpy(c->v_host + parts_at, g.parts.data(), sizeof(ib::Part) * np);
+        const ic::Entry* d_ents = reinterpret_cast<const ic::Entry*>(c->v_dev);
+        const ib::Part* d_parts = reinterpret_cast<const ib::Part*>(c->v_dev + parts_at);
+        uint64_t* d_lim = reinterpret_cast<uint64_t*>(c->v_dev + lim_at);
+        ic::Rec* d_recs = reinterpret_cast<ic::Rec*>(c->v_dev + rec_at);
+        uint16_t* d_sym = reinterpret_cast<uint16_t*>(c->t_dev + sym_at);
+        HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, parts_at + sizeof(ib::Part) * np, hipMemcpyHostToDevice, st));
+        if (g.parts[0].carried) {
+            if (first) return MI355_E_HIP;  // (never: a set's first group begins with a member)
+            HIPCHK(c, hipMemcpyAsync(c->t_dev, c->mp_dev + 256, it::WIN, hipMemcpyDeviceToDevice, st));
+        }
+        HIPCHK(c, pclk.mark(0));
+        hipLaunchKernelGGL(k_inflate_mtab, dim3((uint32_t)k), dim3(64), 0, st, d_parts, d_ents, d_sym, d_recs);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, pclk.mark(1));
+        hipLaunchKernelGGL(k_inflate_mtab_window, dim3((uint32_t)np), dim3(1024), 0, st, d_parts, d_ents, d_recs, d_sym, c->t_dev, (uint32_t)k, d_lim);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, pclk.mark(2));
+        if (g.syms) {
+            hipLaunchKernelGGL(k_inflate_mtab_resolve, dim3(cdiv(g.syms, 256 * it::RESOLVE_RUN)), dim3(256), 0, st, d_parts, (uint32_t)np, d_ents, d_lim,
+                               d_sym, c->t_dev, g.syms);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, pclk.mark(3));
+        if (g.carry_out) HIPCHK(c, hipMemcpyAsync(c->mp_dev + 256, c->t_dev + k * it::WIN, it::WIN, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(ic::Rec) * k, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));  // the one wait of a group
+        pclk.lap(0, 1, 2), pclk.lap(1, 2, 3), pclk.lap(2, 3, 4);
+        memcpy(got.data(), c->v_host + rec_at, sizeof(ic::Rec) * k);
+        return MI355_OK;
+    }
+    // one launch of k_inflate_chain: the one wave, member after member
+    int serial(uint64_t o, uint64_t p, bool ignore_hints, uint32_t behind, uint32_t room, std::vector<im::Member>& rows, std::vector<iw::Rec>& got,
+               im::ChainEnd& e) {
+        if (!room || room > CHAIN_ROOM) return MI355_E_HIP;  // (never)
         const size_t rec_at = align_up(sizeof(im::Member) * CHAIN_ROOM, 256), end_at = align_up(rec_at + sizeof(iw::Rec) * CHAIN_ROOM, 256);
         if (const int rc = ensure_buf(c, &c->m_rows, &c->m_rows_cap, end_at + sizeof(im::ChainEnd))) return rc;
-        const ChainArgs a{s, n, o, p, out, out_cap, ignore_hints ? 1u : 0u, CHAIN_ROOM};
+        const ChainArgs a{s, n, o, p, out, out_cap, ignore_hints ? 1u : 0u, room, behind, 0u};
         HIPCHK(c, clk.mark(0));
         hipLaunchKernelGGL(k_inflate_chain, dim3(1), dim3(64), 0, st, a, reinterpret_cast<im::Member*>(c->m_rows),
                            reinterpret_cast<iw::Rec*>(c->m_rows + rec_at), reinterpret_cast<im::ChainEnd*>(c->m_rows + end_at));
@@ -222,12 +323,20 @@ bool members_args_bad(const void* stream, size_t stream_len, const void* out, si
     return !report || !out_len || (!stream && stream_len) || (!out && out_cap) || (!members && members_cap);
 }
 
+// a members call refused for its arguments: no other call's counters stay behind it
+int members_refuse(mi355_deflate_ctx* c) {
+    if (c)
+        for (int k = 0; k < 6; k++) c->mp_stats[k] = 0;
+    return tabled_refuse(c, "inflate members: bad argument");
+}
+
 // one file, device resident, its arguments checked by the entry; *valid: the bytes of d_out that hold data
 int members_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len, uint8_t* d_out, size_t out_cap, size_t* out_len,
                 mi355_member_info* members, size_t members_cap, size_t* n_members, mi355_inflate_report* report, hipStream_t st,
                 uint64_t* valid) {
     const auto t0 = std::chrono::steady_clock::now();
     c->m_cands.clear(), c->m_walks.clear();
+    for (int k = 0; k < 6; k++) c->mp_stats[k] = 0;  // (first: a call that fails leaves no other call's counters)
     const uint64_t S = c->member_span, n_spans = im::im_n_spans(stream_len, S);
     if (n_spans > 0x7fffffffull) {
         c->err = "inflate members: the file has too many spans";
@@ -236,17 +345,22 @@ int members_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_len
     StageClocks<6, 2> clk{c->m_ev, c->m_ev_ok, c->m_ms, st, stage_clocks_on(c, stream_len)};
     int rc = clk.begin(c);
     if (rc) return rc;
+    StageClocks<5, 4> pclk{c->mp_ev, c->mp_ev_ok, c->mp_ms, st, stage_clocks_on(c, stream_len)};
+    rc = pclk.begin(c);
+    if (rc) return rc;
     // [candidate n] | [Walk n] | [Seg n]
     const size_t walk_at = align_up(sizeof(uint64_t) * n_spans, 256), seg_at = align_up(walk_at + sizeof(im::Walk) * n_spans, 256);
     rc = ensure_buf(c, &c->m_dev, &c->m_dev_cap, seg_at + sizeof(im::Seg) * n_spans);
     if (rc) return rc;
-    MemberDev be{c, d_stream, stream_len, d_out, out_cap, S, n_spans, st, clk};
+    MemberDev be{c, d_stream, stream_len, d_out, out_cap, S, n_spans, st, clk, pclk};
     be.d_cand = reinterpret_cast<uint64_t*>(c->m_dev);
     be.d_walk = reinterpret_cast<im::Walk*>(c->m_dev + walk_at);
     be.d_seg = reinterpret_cast<im::Seg*>(c->m_dev + seg_at);
     std::vector<im::Member> mem;
     std::vector<iw::Rec> recs;
     rc = im::im_run(be, stream_len, S, mem, recs);
+    const uint64_t par[6] = {be.stats.parallel, be.stats.handed, be.stats.spans, be.stats.walkers, be.stats.entries, be.stats.sets};
+    for (int k = 0; k < 6; k++) c->mp_stats[k] = par[k];
     if (rc) return rc;
     uint64_t total = 0;
     if (!(im::im_total(mem, total) && total > out_cap)) {  // (longer than the room: no checksum is judged, as in mi355_inflate)
@@ -271,7 +385,7 @@ int mi355_inflate_members_device(mi355_deflate_ctx* c, const void* d_stream, siz
                                  mi355_member_info* members, size_t members_cap, size_t* n_members, mi355_inflate_report* report,
                                  void* hip_stream) {
     if (members_args_bad(d_stream, stream_len, d_out, out_cap, out_len, members, members_cap, report))
-        return tabled_refuse(c, "inflate members: bad argument");
+        return members_refuse(c);
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
@@ -286,7 +400,7 @@ int mi355_inflate_members_device(mi355_deflate_ctx* c, const void* d_stream, siz
 int mi355_inflate_members(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, uint8_t* out, size_t out_cap, size_t* out_len,
                           mi355_member_info* members, size_t members_cap, size_t* n_members, mi355_inflate_report* report) {
     if (members_args_bad(stream, stream_len, out, out_cap, out_len, members, members_cap, report))
-        return tabled_refuse(c, "inflate members: bad argument");
+        return members_refuse(c);
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
@@ -300,6 +414,22 @@ int mi355_inflate_members(mi355_deflate_ctx* c, const uint8_t* stream, size_t st
 int mi355_inflate_members_last_stages(mi355_deflate_ctx* c, float ms[6]) {
     if (!c || !ms) return MI355_E_ARG;
     for (int k = 0; k < 6; k++) ms[k] = c->m_ms[k];
+    return MI355_OK;
+}
+
+// The large plain members of the context's last members call (MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES): members decoded by the
+// parallel path, members handed back to the one-wave chain, index spans searched, walkers launched, table entries decoded, launch sets
+int mi355_inflate_members_last_parallel(mi355_deflate_ctx* c, uint64_t v[6]) {
+    if (!c || !v) return MI355_E_ARG;
+    for (int k = 0; k < 6; k++) v[k] = c->mp_stats[k];
+    return MI355_OK;
+}
+
+// ... and their HIP-event milliseconds per launch kind, summed over the call's launches: discovery find, discovery walk, tabled
+// decode, window chains, resolve; zeros unless the stage clocks were on (MI355_CFG_STAGE_CLOCKS)
+int mi355_inflate_members_last_parallel_stages(mi355_deflate_ctx* c, float ms[5]) {
+    if (!c || !ms) return MI355_E_ARG;
+    for (int k = 0; k < 5; k++) ms[k] = c->mp_ms[k];
     return MI355_OK;
 }
 

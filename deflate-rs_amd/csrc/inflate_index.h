@@ -35,6 +35,8 @@ constexpr uint64_t SPAN_MAX = 1ull << 30;
 constexpr uint64_t SPAN_DEFAULT = 16384;    // (the best of 16 .. 128 KiB on 100 MB of text from zlib -6: DESIGN.md section 14)
 constexpr uint64_t BIAS = 1ull << 62;        // where a walker's output count begins: no distance is ever larger than it
 enum : uint32_t { END_LINK = 0, END_FINAL = 1, END_FAILED = 2, END_NONE = 3 };  // (NONE: the span has no candidate, nothing walked)
+constexpr uint32_t END_EDGE = 4;             // a walker of a bounded extent (inflate_bigmembers.h) at a boundary at or beyond its edge
+constexpr uint64_t NOEDGE = ~0ull;           // the extent of a whole stream has no edge
 
 // what a walker leaves
 struct Walk {
@@ -112,9 +114,11 @@ MI355_IC uint64_t ix_find_span(Tables& t, const uint8_t* stream, uint64_t stream
 }
 
 // ---- walk: the blocks from candidate c of span k on (sibling of iw_inflate's loop; iw's blocks with a sink that holds nothing) -----
+// edge: the spans below it have been searched (cand[j] is read for j < min(n_spans, edge) only); a boundary in span `edge` or behind it
+// ends the walk as END_EDGE, with the count up to there.  NOEDGE: the whole stream was searched.
 template <class P>
-MI355_IC void ix_walk(Tables& t, const uint8_t* s, uint64_t nbytes, const uint64_t* cand, uint64_t n_spans, uint64_t S, uint64_t k, uint64_t c,
-                      Walk& r) {
+MI355_IC void ix_walk_to(Tables& t, const uint8_t* s, uint64_t nbytes, const uint64_t* cand, uint64_t n_spans, uint64_t S, uint64_t k, uint64_t c,
+                         uint64_t edge, Walk& r) {
     Bits b = ic_bits(s, nbytes, c);
     iw::Sink o{nullptr, 0, 0};
     uint64_t p = BIAS;
@@ -161,6 +165,10 @@ MI355_IC void ix_walk(Tables& t, const uint8_t* s, uint64_t nbytes, const uint64
         }
         // a boundary: does the walker of the span it lies in begin here?
         const uint64_t j = b.pos / (8 * S);
+        if (j >= edge) {
+            r.how = END_EDGE;
+            break;
+        }
         if (j > k && j < n_spans && P::stop(b.pos, cand[j])) {
             r.how = END_LINK, r.link = (uint32_t)j;
             break;
@@ -174,6 +182,11 @@ MI355_IC void ix_walk(Tables& t, const uint8_t* s, uint64_t nbytes, const uint64
     }
     r.status = f.status, r.bit = f.bit, r.in_pos = r.count = f.in_pos - BIAS;
     r.n_blocks = 0, r.n_stored = r.n_fixed = r.n_dynamic = 0;
+}
+template <class P>
+MI355_IC void ix_walk(Tables& t, const uint8_t* s, uint64_t nbytes, const uint64_t* cand, uint64_t n_spans, uint64_t S, uint64_t k, uint64_t c,
+                      Walk& r) {
+    ix_walk_to<P>(t, s, nbytes, cand, n_spans, S, k, c, NOEDGE, r);
 }
 // ... of one framed stream: what a workgroup of the walk kernel does (c: the span's candidate, NOCAND: none)
 template <class P>

@@ -258,15 +258,16 @@ MI355_IC void im_member_open(Tables& t, const uint8_t* s, uint64_t n, uint64_t o
 MI355_IC uint8_t* im_out_at(uint8_t* out, uint64_t out_cap, uint64_t p) { return p < out_cap ? out + p : out; }
 MI355_IC uint64_t im_room_at(uint64_t out_cap, uint64_t p) { return p < out_cap ? out_cap - p : 0; }
 
-// what the one wave of the chain kernel does: members from (o, p) on into rows[0, room) / recs[0, room)
+// what the one wave of the chain kernel does: members from (o, p) on into rows[0, room) / recs[0, room).  behind: members that the
+// same launch set has walked in front of o by other means (inflate_bigmembers.h) -- a hinted header at o itself then stops the chain too
 template <class P>
-MI355_IC void im_chain(Tables& t, const uint8_t* s, uint64_t n, uint64_t o, uint64_t p, uint8_t* out, uint64_t out_cap, bool ignore_hints,
-                       Member* rows, iw::Rec* recs, uint32_t room, ChainEnd& e) {
+MI355_IC void im_chain_behind(Tables& t, const uint8_t* s, uint64_t n, uint64_t o, uint64_t p, uint8_t* out, uint64_t out_cap, bool ignore_hints,
+                              uint32_t behind, Member* rows, iw::Rec* recs, uint32_t room, ChainEnd& e) {
     e = ChainEnd{o, p, 0, STOP_ROOM};
     for (uint32_t m = 0; m < room; m++) {
         uint64_t t_, in_len;
         uint32_t z_;
-        if (m && !ignore_hints && im_hint<P>(s, n, e.o, t_, z_)) {
+        if ((m || behind) && !ignore_hints && im_hint<P>(s, n, e.o, t_, z_)) {
             e.how = STOP_HINT;
             return;
         }
@@ -288,6 +289,11 @@ MI355_IC void im_chain(Tables& t, const uint8_t* s, uint64_t n, uint64_t o, uint
             return;
         }
     }
+}
+template <class P>
+MI355_IC void im_chain(Tables& t, const uint8_t* s, uint64_t n, uint64_t o, uint64_t p, uint8_t* out, uint64_t out_cap, bool ignore_hints,
+                       Member* rows, iw::Rec* recs, uint32_t room, ChainEnd& e) {
+    im_chain_behind<P>(t, s, n, o, p, out, out_cap, ignore_hints, 0u, rows, recs, room, e);
 }
 
 // ---- the call: host side of all builds ----------------------------------------------------------------------------------------------------

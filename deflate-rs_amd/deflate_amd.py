@@ -325,6 +325,8 @@ def load():
     L.mi355_inflate_members.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                         C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(InflateReport)]
     L.mi355_inflate_members_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_inflate_members_last_parallel.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mi355_inflate_members_last_parallel_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mi355_inflate_members_last_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(MemberWalk), C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
@@ -357,7 +359,7 @@ EXPORTED = [
     "mi355_inflate_index", "mi355_inflate_index_device", "mi355_inflate_parallel", "mi355_inflate_parallel_device",
     "mi355_inflate_index_last_stages", "mi355_inflate_index_last_walks",
     "mi355_inflate_members", "mi355_inflate_members_device", "mi355_inflate_members_last_stages",
-    "mi355_inflate_members_last_walks",
+    "mi355_inflate_members_last_walks", "mi355_inflate_members_last_parallel", "mi355_inflate_members_last_parallel_stages",
 ]
 
 
@@ -393,6 +395,7 @@ class Context:
     CFG_INFLATE_GROUP_BYTES = 11
     CFG_INFLATE_INDEX_SPAN_BYTES = 12
     CFG_INFLATE_MEMBER_SPAN_BYTES = 13
+    CFG_INFLATE_MEMBER_PARALLEL_BYTES = 14
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -924,6 +927,25 @@ class Context:
         if rc != OK:
             self._err(rc)
         return dict(zip(("find_ms", "walk_ms", "fill_ms", "member_decode_ms", "chain_decode_ms", "checksums_ms"), ms))
+
+    def inflate_members_last_parallel(self):
+        """mi355_inflate_members_last_parallel: what the parallel path of the last members call did (CFG_INFLATE_MEMBER_PARALLEL_BYTES)
+        -- members it decoded, members handed back to the one-wave chain, index spans searched, walkers launched, table entries
+        decoded, launch sets"""
+        v = (C.c_uint64 * 6)()
+        rc = load().mi355_inflate_members_last_parallel(self._h, v)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("parallel", "handed", "spans", "walkers", "entries", "sets"), v))
+
+    def inflate_members_parallel_stages(self):
+        """mi355_inflate_members_last_parallel_stages: HIP-event ms of the parallel path's launch kinds in the last members call
+        (zeros without CFG_STAGE_CLOCKS)"""
+        ms = (C.c_float * 5)()
+        rc = load().mi355_inflate_members_last_parallel_stages(self._h, ms)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("discover_find_ms", "discover_walk_ms", "tabled_decode_ms", "windows_ms", "resolve_ms"), ms))
 
     def inflate_members_walks(self):
         """mi355_inflate_members_last_walks: (candidates, walkers' records as tuples in MemberWalk's field order) of the find and

@@ -169,7 +169,17 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *   MI355_CFG_INFLATE_MEMBER_SPAN_BYTES  compressed bytes of one span of mi355_inflate_members[_device] (default 64 KiB; 16 bytes ..
  *                          1 GiB): one wave searches a span for a member that states its own size and one lane hops on from it.
  *                          Same results either way.  The default is derived, not measured: a BGZF member is 64 KiB at most, so at
- *                          that size every interior span of a BGZF file holds a member start. */
+ *                          that size every interior span of a BGZF file holds a member start.
+ *   MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES  how many compressed bytes must be left in the file from the start of a member that states
+ *                          no size for mi355_inflate_members[_device] to look for its end and its block table on the device and to
+ *                          decode it in parallel (default 64 KiB; 1 KiB .. 1 GiB; 0 switches the path off: every such member is
+ *                          walked by one wave).  Same results either way.  The default is derived, not measured -- four spans of
+ *                          MI355_CFG_INFLATE_INDEX_SPAN_BYTES at its default, so that a table of two entries at least is likely --
+ *                          and no measured optimum.  What tools/inflate_members_bench.py has measured (profiles/
+ *                          inflate_members_bench.json; 100 MB of text as 64 members): finding a member costs about 29 ms whatever
+ *                          its size, so the path wins where one wave would need longer for the member -- deflated text: 2354 ms
+ *                          on, 17 285 ms off -- and LOSES where one wave is fast -- the same members as stored blocks: 1450 ms on,
+ *                          72.7 ms off.  Set 0 for files of stored or hardly compressed members. */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -183,6 +193,7 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_INFLATE_GROUP_BYTES 11
 #define MI355_CFG_INFLATE_INDEX_SPAN_BYTES 12
 #define MI355_CFG_INFLATE_MEMBER_SPAN_BYTES 13
+#define MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES 14
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
@@ -613,8 +624,17 @@ int mi355_inflate_index_last_walks(mi355_deflate_ctx* ctx, mi355_index_walk* out
  *   is decoded by the batched one-wave inflate, member k at the sum of the ISIZEs in front of it.  A hint is a claim and never
  *   trusted for a byte: the run is accepted up to the first member that is not both structurally clean and exactly ISIZE bytes
  *   long, and from there one wave walks member after member, open ended, until a hinted header follows again (at most 8 such
- *   returns a call, which bounds the launches an adversarial file can cost and changes no result).  A large plain member is
- *   walked by one wave, as mi355_inflate walks it.  The checksums: one pass of the batch's checksum launches over the member table. */
+ *   returns a call, which bounds the launches an adversarial file can cost and changes no result).  The checksums: one pass of the
+ *   batch's checksum launches over the member table.
+ *   The third path, for members that state no size (`cat a.gz b.gz`, rotated logs, this library's packed gzip arena): where at
+ *   least MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES are left in the file, the member's end is DISCOVERED -- the finder and the walkers
+ *   of mi355_inflate_index over a bounded extent of MI355_CFG_INFLATE_INDEX_SPAN_BYTES spans behind its header, the extent doubling
+ *   while the chain of walkers runs into its edge -- and with it the member's size, its block table and the next member's start.
+ *   The tables of all members so found are decoded together by the three passes of mi355_inflate_tabled, in groups of
+ *   MI355_CFG_INFLATE_GROUP_BYTES that may hold many members: a wave per table entry, a window chain per member, one resolve.  A
+ *   member found is never trusted for a byte either: the first one that is not clean, in discovery or in decode, and everything
+ *   behind it go back to the one wave, whose results are the call's.  A member shorter than the setting ends discovery, so a file of
+ *   many small plain members costs one discovery a launch of the one wave and not one a member. */
 #define MI355_MEMBER_HINTED 1u   /* the member's size was taken from its BC subfield and found true */
 typedef struct {
     uint64_t in_off, in_len;     /* the member in the file, header through trailer */
@@ -629,6 +649,13 @@ int mi355_inflate_members(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t 
 /* A measuring aid like mi355_inflate_index_last_stages: HIP-event milliseconds of the context's last members call per launch kind,
  * summed over its launches -- find, walk, fill, member decode, chain decode, checksums; zeros unless the stage clocks were on. */
 int mi355_inflate_members_last_stages(mi355_deflate_ctx* ctx, float ms[6]);
+/* Measuring aids and no part of the stable interface: the third path in the context's last members call.  v: members decoded by the
+ * parallel path, members handed back to the one-wave chain, index spans searched, walkers launched, table entries decoded, launch
+ * sets (groups).  ms: HIP-event milliseconds per launch kind, summed over the call's launches -- discovery find, discovery walk,
+ * tabled decode, window chains, resolve; zeros unless the stage clocks were on.  (The one wave's time stays in slot 4 of
+ * mi355_inflate_members_last_stages.) */
+int mi355_inflate_members_last_parallel(mi355_deflate_ctx* ctx, uint64_t v[6]);
+int mi355_inflate_members_last_parallel_stages(mi355_deflate_ctx* ctx, float ms[5]);
 /* A measuring aid like mi355_inflate_index_last_walks and no part of the stable interface: what the find and the first walk of the
  * context's last members call (the run from byte 0) left on the device, one of each per span of the file -- cand[k], the span's
  * candidate (UINT64_MAX: none), and walks[k], its walker's record.  *n_spans = their count (0 behind an empty file or a call that

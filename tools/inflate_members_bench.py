@@ -9,7 +9,12 @@ the 28-byte end-of-file marker.
   sweep     the call at MI355_CFG_INFLATE_MEMBER_SPAN_BYTES = 16 KiB .. 1 MiB, alternating; which span size wins
   batch     mi355_inflate_batch_device handed the true member table from the host: the same decode without discovery
   parallel  mi355_inflate_parallel_device on the same text as ONE gzip member (zlib level 6)
-  cat       mi355_inflate_members_device on a `cat` of 64 plain members of the same text: Path B's cost, run once (--cat 0 leaves it out)
+  cat       mi355_inflate_members_device on a `cat` of 64, 8 and 512 plain members of the same text (--cat 0 leaves it out): the call
+            with MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES at its default against mi355_inflate_parallel_device on the one member,
+            alternating; its counters (mi355_inflate_members_last_parallel) and, from a context with the stage clocks on, its
+            milliseconds per launch kind; and, on the 64 members, the same call with the setting at 0 -- the one wave, run once
+  stored    the same 64 members as STORED blocks (zlib level 0), which one wave copies fast: the call with the setting at its default
+            and at 0, alternating -- where the parallel path's fixed cost per member shows against the cheapest members there are
 Every timed call returns after its stream has drained; every output is compared with the input once, outside the timing.
 Writes profiles/inflate_members_bench.json (--out) and prints the same JSON line.  --size N: bytes of the text (default 100 000 000)."""
 import argparse
@@ -32,6 +37,7 @@ import deflate_amd as da  # noqa: E402
 
 SWEEP = tuple(16 << (10 + k) for k in range(7))  # 16 KiB .. 1 MiB
 SPAN_DEFAULT = 64 << 10                          # the default of MI355_CFG_INFLATE_MEMBER_SPAN_BYTES
+PARALLEL_DEFAULT = 64 << 10                      # the default of MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES
 BLOCK = 0xff00
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
@@ -49,8 +55,8 @@ def bgzf_member(data):
             struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
-def plain_member(data):
-    return (bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff]) + raw_deflate(data) + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF))
+def plain_member(data, level=6):
+    return (bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff]) + raw_deflate(data, level) + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data) & 0xFFFFFFFF))
 
 
 def alternate(fns, reps):
@@ -154,16 +160,56 @@ def main():
     r["sweep"] = {str(S): {"ms": round(sweep[S][0], 3), "spread_ms": round(sweep[S][1], 3)} for S in SWEEP}
     r["sweep_best_span_bytes"] = min(SWEEP, key=lambda S: sweep[S][0])
     res["bgzf"] = r
-    if a.cat:
-        step = (len(data) + 63) // 64
+    for k in (64, 8, 512) if a.cat else ():
+        step = (len(data) + k - 1) // k
         cat = b"".join(plain_member(data[o: o + step]) for o in range(0, len(data), step))
         d_cat = dev(cat)
-        d_out.zero_()
-        t0 = time.perf_counter()
+        fns = {"members": lambda: members(d_cat, len(cat)), "parallel_one_member": parallel}
+        t = alternate(fns, a.reps)
+        for fn in fns.values():
+            check(fn)
         members(d_cat, len(cat))
-        ms = (time.perf_counter() - t0) * 1e3
-        assert torch.equal(d_out, d_in) and nm.value == 64
-        res["cat_64_plain_members"] = {"file_bytes": len(cat), "members": nm.value, "ms": round(ms, 1), "gbps": round(len(data) / ms / 1e6, 3)}
+        assert nm.value == k
+        r = {"file_bytes": len(cat), "members": nm.value, "parallel_bytes": PARALLEL_DEFAULT, "ms": round(t["members"][0], 3),
+             "spread_ms": round(t["members"][1], 3), "gbps": round(len(data) / t["members"][0] / 1e6, 3),
+             "parallel_one_member_ms": round(t["parallel_one_member"][0], 3),
+             "over_one_member": round(t["members"][0] / t["parallel_one_member"][0], 3), "counters": ctx.inflate_members_last_parallel()}
+        clk = da.Context(0)
+        clk.config(da.Context.CFG_STAGE_CLOCKS, 1)
+        rows = []
+        for _ in range(a.reps + 1):
+            members(d_cat, len(cat), clk._h)
+            rows.append(dict(clk.inflate_members_stages(), **clk.inflate_members_parallel_stages()))
+        r["stages"] = {name: round(min(row[name] for row in rows[1:]), 3) for name in rows[0]}
+        clk.close()
+        if k == 64:  # the setting at 0: every member by the one wave, once
+            ctx.config(da.Context.CFG_INFLATE_MEMBER_PARALLEL_BYTES, 0)
+            d_out.zero_()
+            t0 = time.perf_counter()
+            members(d_cat, len(cat))
+            ms = (time.perf_counter() - t0) * 1e3
+            ctx.config(da.Context.CFG_INFLATE_MEMBER_PARALLEL_BYTES, PARALLEL_DEFAULT)
+            assert torch.equal(d_out, d_in) and nm.value == k and not any(ctx.inflate_members_last_parallel().values())
+            r["off_ms"], r["off_gbps"] = round(ms, 1), round(len(data) / ms / 1e6, 3)
+        res["cat_%d_plain_members" % k] = r
+    if a.cat:
+        step = (len(data) + 63) // 64
+        cat = b"".join(plain_member(data[o: o + step], 0) for o in range(0, len(data), step))
+        d_cat = dev(cat)
+
+        def at(v):
+            def run():
+                ctx.config(da.Context.CFG_INFLATE_MEMBER_PARALLEL_BYTES, v)
+                members(d_cat, len(cat))
+            return run
+        fns = {"on": at(PARALLEL_DEFAULT), "off": at(0)}
+        t = alternate(fns, a.reps)
+        for fn in fns.values():
+            check(fn)
+        at(PARALLEL_DEFAULT)()
+        res["cat_64_stored_members"] = {"file_bytes": len(cat), "members": nm.value, "ms": round(t["on"][0], 3), "spread_ms": round(t["on"][1], 3),
+                                        "off_ms": round(t["off"][0], 3), "off_spread_ms": round(t["off"][1], 3),
+                                        "counters": ctx.inflate_members_last_parallel()}
     ctx.close()
     line = json.dumps(res)
     print(line)
