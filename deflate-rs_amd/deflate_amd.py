@@ -188,6 +188,23 @@ class MemberWalk(C.Structure):
                 ("how", C.c_uint32), ("link", C.c_uint32)]
 
 
+class SeekInfo(C.Structure):
+    """mi355_seek_info (56 bytes)"""
+    _fields_ = [("total", C.c_uint64), ("n_entries", C.c_uint64), ("n_points", C.c_uint64), ("spacing", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("stream_len", C.c_uint64), ("wrapper", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SeekPoint(C.Structure):
+    """mi355_seek_point (16 bytes): a point's raw-deflate bit offset and output position"""
+    _fields_ = [("bit", C.c_uint64), ("pos", C.c_uint64)]
+
+
+class SeekRange(C.Structure):
+    """mi355_seek_range (40 bytes): one range of mi355_inflate_seek_read_batch_device"""
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("out", C.c_void_p), ("got", C.c_uint64), ("status", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -328,6 +345,20 @@ def load():
     L.mi355_inflate_members_last_parallel.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mi355_inflate_members_last_parallel_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mi355_inflate_members_last_walks.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(MemberWalk), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_inflate_seek_build_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t, C.c_uint64,
+                                                  C.POINTER(C.c_void_p), C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_seek_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(BlockInfo), C.c_size_t, C.c_uint64,
+                                           C.POINTER(C.c_void_p), C.POINTER(InflateReport)]
+    L.mi355_inflate_seek_free.argtypes = [C.c_void_p]
+    L.mi355_inflate_seek_free.restype = None
+    L.mi355_inflate_seek_info.argtypes = [C.c_void_p, C.POINTER(SeekInfo)]
+    L.mi355_inflate_seek_points.argtypes = [C.c_void_p, C.POINTER(SeekPoint), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_inflate_seek_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                                 C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_seek_read.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(InflateReport)]
+    L.mi355_inflate_seek_read_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SeekRange), C.c_size_t, C.POINTER(InflateReport),
+                                                       C.c_void_p]
+    L.mi355_inflate_seek_last_read.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -360,7 +391,118 @@ EXPORTED = [
     "mi355_inflate_index_last_stages", "mi355_inflate_index_last_walks",
     "mi355_inflate_members", "mi355_inflate_members_device", "mi355_inflate_members_last_stages",
     "mi355_inflate_members_last_walks", "mi355_inflate_members_last_parallel", "mi355_inflate_members_last_parallel_stages",
+    "mi355_inflate_seek_build", "mi355_inflate_seek_build_device", "mi355_inflate_seek_free", "mi355_inflate_seek_info",
+    "mi355_inflate_seek_points", "mi355_inflate_seek_read", "mi355_inflate_seek_read_device", "mi355_inflate_seek_read_batch_device",
+    "mi355_inflate_seek_last_read",
 ]
+
+
+class SeekIndex:
+    """A seek index of one stream (mi355_inflate_seek): its table and the 32 KiB window in front of some of its entries, for reads of
+    byte ranges.  Made by Context.inflate_seek (host bytes: the handle keeps a device copy of the stream) or
+    Context.inflate_seek_device (the caller passes the stream's device pointer again at every read)."""
+
+    def __init__(self, ctx, handle, report):
+        self._ctx, self._h, self.report = ctx, handle, report
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().mi355_inflate_seek_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """mi355_inflate_seek_info"""
+        i = SeekInfo()
+        rc = load().mi355_inflate_seek_info(self._h, C.byref(i))
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return {k: getattr(i, k) for k, _ in SeekInfo._fields_ if k != "reserved"}
+
+    def points(self):
+        """mi355_inflate_seek_points: [(bit, pos)] of the points, entry 0 first"""
+        n = C.c_size_t(0)
+        load().mi355_inflate_seek_points(self._h, None, 0, C.byref(n))
+        arr = (SeekPoint * max(n.value, 1))()
+        rc = load().mi355_inflate_seek_points(self._h, arr, n.value, C.byref(n))
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return [(arr[k].bit, arr[k].pos) for k in range(n.value)]
+
+    def last_read(self):
+        """mi355_inflate_seek_last_read: what the last read did, from its plan"""
+        v = (C.c_uint64 * 4)()
+        rc = load().mi355_inflate_seek_last_read(self._h, v)
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return dict(zip(("entries", "symbols", "steps", "sets"), v))
+
+    def read_raw(self, off, length):
+        """mi355_inflate_seek_read on a handle of Context.inflate_seek: (rc, report dict, the bytes that hold data); rc is OK or E_DATA"""
+        out = C.create_string_buffer(max(length, 1))
+        got, r = C.c_uint64(0), InflateReport()
+        rc = load().mi355_inflate_seek_read(self._h, off, length, C.cast(out, C.c_void_p) if length else None, C.byref(got), C.byref(r))
+        if rc not in (OK, E_DATA):
+            self._ctx._err(rc)
+        return rc, r.as_dict(), out.raw[:got.value]
+
+    def read(self, off, length):
+        """pread: the stream's bytes [off, off + length), fewer at its end; DeflateError(E_DATA, ...) if the stream no longer decodes"""
+        rc, _rep, data = self.read_raw(off, length)
+        if rc != OK:
+            self._ctx._err(rc)
+        return data
+
+    def read_device(self, off, length, d_out_ptr, d_stream_ptr=0, stream=0, check=False):
+        """mi355_inflate_seek_read_device: (rc, got, report dict).  d_stream_ptr 0: the handle's own copy of the stream."""
+        got, r = C.c_uint64(0), InflateReport()
+        rc = load().mi355_inflate_seek_read_device(self._h, C.c_void_p(d_stream_ptr), off, length, C.c_void_p(d_out_ptr), C.byref(got),
+                                                   C.byref(r), C.c_void_p(stream))
+        if rc not in (OK, E_DATA) or (check and rc != OK):
+            self._ctx._err(rc)
+        return rc, got.value, r.as_dict()
+
+    def read_batch_device(self, ranges, d_stream_ptr=0, stream=0, check=False):
+        """mi355_inflate_seek_read_batch_device: ranges = [(off, len, d_out_ptr)], all through one launch set.  Returns (rc, [(status,
+        got, report dict)])."""
+        n = len(ranges)
+        arr = (SeekRange * max(n, 1))()
+        for k, (off, length, ptr) in enumerate(ranges):
+            arr[k].off, arr[k].len, arr[k].out = off, length, ptr
+        reps = (InflateReport * max(n, 1))()
+        rc = load().mi355_inflate_seek_read_batch_device(self._h, C.c_void_p(d_stream_ptr), arr, n, reps, C.c_void_p(stream))
+        if rc not in (OK, E_DATA) or (check and rc != OK):
+            self._ctx._err(rc)
+        return rc, [(arr[k].status, arr[k].got, reps[k].as_dict()) for k in range(n)]
+
+    def read_batch(self, ranges):
+        """[(off, len), ...] -> [bytes, ...]: one launch set for all of them, through a device buffer of this call"""
+        import torch
+
+        total = sum(length for _off, length in ranges)
+        buf = torch.empty(max(total, 1), dtype=torch.uint8, device="cuda:%d" % self._ctx.device)
+        at, items = 0, []
+        for off, length in ranges:
+            items.append((off, length, buf.data_ptr() + at if length else 0))
+            at += length
+        _rc, res = self.read_batch_device(items, check=True)
+        host = buf.cpu().numpy().tobytes()
+        out, at = [], 0
+        for (_off, length), (_st, got, _rep) in zip(ranges, res):
+            out.append(host[at:at + got])
+            at += length
+        return out
 
 
 class Context:
@@ -676,6 +818,27 @@ class Context:
                                                         C.c_void_p(ptr_len(table)[0] if table is not None else 0), C.byref(used),
                                                         C.c_void_p(stream))
         return self._packed_result(arena, ap, items, n, used.value, rc, check)
+
+    # ---- seek points: byte ranges of one large stream (mi355_inflate_seek_*) ----
+    def _seek(self, call):
+        h, r = C.c_void_p(), InflateReport()
+        rc = call(C.byref(h), C.byref(r))
+        if rc != OK:
+            self._err(rc)
+        return SeekIndex(self, h, r.as_dict())
+
+    def inflate_seek(self, stream, wrapper=0, spacing=0, blocks=None):
+        """mi355_inflate_seek_build on host bytes -> SeekIndex.  spacing: output bytes between points, 0 = 1 MiB; blocks: the stream's
+        table (Context.blocks()), else the device finds one.  A stream that does not decode raises DeflateError(E_DATA, ...)."""
+        arr, nb = self._block_table(blocks)
+        stream = bytes(stream)
+        return self._seek(lambda h, r: load().mi355_inflate_seek_build(self._h, stream, len(stream), wrapper, arr, nb, spacing, h, r))
+
+    def inflate_seek_device(self, d_stream_ptr, stream_len, wrapper=0, spacing=0, blocks=None, stream=0):
+        """mi355_inflate_seek_build_device: the same for a stream in device memory, which the handle does not keep"""
+        arr, nb = self._block_table(blocks)
+        return self._seek(lambda h, r: load().mi355_inflate_seek_build_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, arr, nb,
+                                                                             spacing, h, r, C.c_void_p(stream)))
 
     # ---- verify: does the stream inflate to the input? (mi355_deflate_verify*) ----
     @staticmethod

@@ -3,6 +3,7 @@
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
  *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
  *   mi355_deflate_cli -d --members [-gzip] IN OUT
+ *   mi355_deflate_cli -d --range OFF:LEN [-raw|-zlib|-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
  * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
@@ -11,6 +12,9 @@
  * two calls are mi355_inflate_parallel: the block table of the stream is found on the GPU and every entry decoded by a wave of its own
  * (the way for one large file from anywhere); the result is the same.  With --members IN is a gzip FILE of any number of members --
  * BGZF, `cat a.gz b.gz` -- and the two calls are mi355_inflate_members (plain -d -gzip takes exactly one member); --members with -raw or -zlib is refused with the usage text.
+ * With --range OFF:LEN only the bytes [OFF, OFF + LEN) of what IN inflates to are written (fewer at its end, like pread): a seek index
+ * is built (mi355_inflate_seek_build: the table found on the GPU, a window kept every MiB of output) and the range is decoded from the
+ * nearest point (mi355_inflate_seek_read); not together with --parallel or --members.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
  *             -Wl,-rpath,$PWD/deflate-rs_amd -o /tmp/mi355_deflate_cli */
 #include <stdio.h>
@@ -27,7 +31,8 @@ static int fail(const char* what, int rc, mi355_deflate_ctx* ctx) {
 int main(int argc, char** argv) {
     int wrapper = 0, level = 1;
     size_t chunk = 0;
-    int verify = 0, decompress = 0, parallel = 0, members = 0, format_given = 0;
+    int verify = 0, decompress = 0, parallel = 0, members = 0, format_given = 0, ranged = 0;
+    unsigned long long r_off = 0, r_len = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "-raw")) wrapper = 0, format_given = 1;
@@ -40,13 +45,23 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[a], "-d") || !strcmp(argv[a], "--decompress")) decompress = 1;
         else if (!strcmp(argv[a], "--parallel") || !strcmp(argv[a], "-parallel")) parallel = 1;
         else if (!strcmp(argv[a], "--members") || !strcmp(argv[a], "-members")) members = 1;
-        else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
+        else if ((!strcmp(argv[a], "--range") || !strcmp(argv[a], "-range")) && a + 1 < argc) {
+            char* end = NULL;
+            r_off = strtoull(argv[++a], &end, 10);
+            ranged = end && *end == ':' && end != argv[a] && end[1] ? 1 : -1;
+            if (ranged == 1) {
+                const char* tail = end + 1;
+                r_len = strtoull(tail, &end, 10);
+                if (*end) ranged = -1;
+            }
+        } else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
     /* --members is gzip by definition: another format switch beside it is refused, not ignored */
-    if (argc - a != 2 || ((parallel || members) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2)) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n",
-                argv[0], argv[0], argv[0]);
+    if (argc - a != 2 || ((parallel || members || ranged) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2) ||
+        ranged < 0 || (ranged && (parallel || members))) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [-raw|-zlib|-gzip] IN OUT\n",
+                argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     FILE* f = fopen(argv[a], "rb");
@@ -84,6 +99,40 @@ int main(int argc, char** argv) {
                 (unsigned long)got, (unsigned long)n_members, (unsigned long long)r.n_blocks, r.n_stored, r.n_fixed, r.n_dynamic, r.ms);
         free(data);
         free(in);
+        mi355_deflate_ctx_destroy(ctx);
+        return 0;
+    }
+    if (decompress && ranged) { /* a seek index of the stream, then the one range from its nearest point */
+        mi355_inflate_report r;
+        mi355_inflate_seek* seek = NULL;
+        mi355_seek_info si;
+        uint64_t got = 0;
+        rc = mi355_inflate_seek_build(ctx, in, n, wrapper, NULL, 0, 0, &seek, &r);
+        const float build_ms = r.ms;
+        if (rc == MI355_OK) rc = mi355_inflate_seek_info(seek, &si);
+        uint8_t* data = NULL;
+        if (rc == MI355_OK) {
+            if (r_off > si.total) r_off = si.total;
+            if (r_len > si.total - r_off) r_len = si.total - r_off;
+            data = (uint8_t*)malloc(r_len ? (size_t)r_len : 1);
+            if (!data) return fail("malloc", -1, NULL);
+            rc = mi355_inflate_seek_read(seek, r_off, r_len, data, &got, &r);
+        }
+        if (rc == MI355_E_DATA) {
+            fprintf(stderr, "inflate: status %u at bit %llu, output byte %llu\n%s\n", r.status, (unsigned long long)r.bit,
+                    (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
+            return 3;
+        }
+        if (rc) return fail("mi355_inflate_seek", rc, ctx);
+        f = fopen(argv[a + 1], "wb");
+        if (!f || fwrite(data, 1, (size_t)got, f) != (size_t)got) return fail("write output", -1, NULL);
+        fclose(f);
+        fprintf(stderr, "%lu -> bytes [%llu, %llu) of %llu, %llu entries, %llu points, index %.3f ms, read %.3f ms\n", (unsigned long)n, r_off,
+                r_off + (unsigned long long)got, (unsigned long long)si.total, (unsigned long long)si.n_entries, (unsigned long long)si.n_points,
+                build_ms, r.ms);
+        free(data);
+        free(in);
+        mi355_inflate_seek_free(seek);
         mi355_deflate_ctx_destroy(ctx);
         return 0;
     }

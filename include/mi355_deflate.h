@@ -670,6 +670,75 @@ typedef struct {
 } mi355_member_walk; /* 40 bytes */
 int mi355_inflate_members_last_walks(mi355_deflate_ctx* ctx, uint64_t* cand, mi355_member_walk* walks, size_t cap, size_t* n_spans);
 
+/* ---- seek points: any byte range of ONE large stream, decoded from the nearest restart point ---------------
+ * mi355_inflate_parallel gives back a whole stream; these calls give back PART of one without an output buffer for the rest and
+ * without decoding the rest.  A handle keeps the stream's table (the caller's, or the one mi355_inflate_index finds) and, for some
+ * of its entries -- the POINTS --, the resolved 32 KiB of output in front of them: decoding from a point needs nothing before it.
+ * Point rule: entry 0 is a point (its window is zeros and is not stored); entry k > 0 is a point iff its output position lies
+ *   `spacing` bytes or more behind the last point's.  spacing: output bytes, 0 = 1 MiB (zran's convention; derived, not measured),
+ *   else 32 KiB to 1 GiB; anything else is MI355_E_ARG.  A handle holds 16 bytes per entry on the host and 32 KiB per point on the
+ *   device (mi355_inflate_seek_info).
+ * _build[_device]: the tabled decode of the whole stream, group by group (MI355_CFG_INFLATE_GROUP_BYTES), without an output buffer.
+ *   blocks == NULL (or n_blocks == 0): the table is found as mi355_inflate_index finds it; else the caller's table under
+ *   mi355_inflate_tabled's rules.  Every structural status of mi355_inflate_tabled (MI355_VERIFY_TABLE included) is the build's, and
+ *   for wrapper 1 / 2 every group is resolved into a scratch region, summed by the checksum kernels, and the sums are folded
+ *   (mi355_checksum_combine) and compared with the trailer and ISIZE: MI355_VERIFY_CHECKSUM.  Because the sums are per group a framed
+ *   stream may inflate to more than 4 GiB - 64 KiB; a single GROUP above that is MI355_E_UNSUPPORTED.  A stream that fails:
+ *   MI355_E_DATA, the report, *seek = NULL.  MI355_OK: report.out_len = the stream's size and *seek is the handle, to be freed with
+ *   mi355_inflate_seek_free before its context is destroyed.  Argument errors are decided before a context or the device is touched;
+ *   a live shard is MI355_E_STATE; build and reads leave mi355_deflate_last_info / _last_blocks / _last_batch_info alone.
+ *   _device never keeps the stream: the caller passes it again at each read.  The host form keeps a device copy in the handle
+ *   (d_stream = NULL at a _device read means that copy), and mi355_inflate_seek_read copies the bytes back.
+ * _read*: pread.  *got = min(len, total - off), 0 when off >= total -- which is MI355_OK, as is len == 0.  MI355_OK: out[0, got) are
+ *   the stream's bytes [off, off + got); report.out_len = got, report.out_pos = the stream position reached, the block counts are
+ *   those of the entries decoded.  The range decodes the entries from the last point at or before `off` through the entry that holds
+ *   its last byte; a range of more than MI355_CFG_INFLATE_GROUP_BYTES symbols is cut at points into pieces, each from its own point.
+ *   If the stream passed no longer decodes as it did at the build: MI355_E_DATA, the report is the first failing entry's among those
+ *   decoded (out_pos a position of the stream), *got = the bytes that hold data, out[0, max(out_pos, off) - off) clipped to len, and
+ *   nothing is stored at or beyond that.  No store ever lands at or beyond out + len.  NO CHECKSUM IS JUDGED ON A READ: damage that
+ *   leaves every decoded entry structurally valid and ending where the table says is not noticed.
+ * _read_batch_device: n ranges through ONE launch set -- three launches and one wait; more sets only when their symbols exceed the
+ *   group budget.  got and status are written per range, reports[i] if reports is not NULL; a failing range disturbs no neighbour; the
+ *   call returns the first failing status.  Overlapping out buffers are undefined. */
+typedef struct mi355_inflate_seek mi355_inflate_seek; /* owns: the table (host), one 32 KiB window per point (device) */
+typedef struct {
+    uint64_t total;        /* bytes the stream inflates to */
+    uint64_t n_entries;    /* of the table */
+    uint64_t n_points;     /* entry 0 included */
+    uint64_t spacing;      /* the one in force */
+    uint64_t device_bytes; /* held on the device: the windows, and the host form's copy of the stream */
+    uint64_t stream_len;
+    uint32_t wrapper, reserved;
+} mi355_seek_info; /* 56 bytes */
+typedef struct {
+    uint64_t bit; /* raw-deflate bit offset of the point's entry */
+    uint64_t pos; /* its output position */
+} mi355_seek_point; /* 16 bytes */
+typedef struct {
+    uint64_t off, len;
+    void* out;        /* device memory, len bytes */
+    uint64_t got;     /* written */
+    int32_t status;   /* written: MI355_OK or MI355_E_DATA */
+    uint32_t reserved;
+} mi355_seek_range; /* 40 bytes */
+int mi355_inflate_seek_build_device(mi355_deflate_ctx* ctx, const void* d_stream, size_t stream_len, int wrapper,
+                                    const mi355_block_info* blocks, size_t n_blocks, uint64_t spacing, mi355_inflate_seek** seek,
+                                    mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_seek_build(mi355_deflate_ctx* ctx, const uint8_t* stream, size_t stream_len, int wrapper,
+                             const mi355_block_info* blocks, size_t n_blocks, uint64_t spacing, mi355_inflate_seek** seek,
+                             mi355_inflate_report* report);
+void mi355_inflate_seek_free(mi355_inflate_seek* seek);
+int mi355_inflate_seek_info(mi355_inflate_seek* seek, mi355_seek_info* info);
+int mi355_inflate_seek_points(mi355_inflate_seek* seek, mi355_seek_point* out, size_t cap, size_t* n); /* cap too small: MI355_E_OUT_TOO_SMALL and *n */
+int mi355_inflate_seek_read_device(mi355_inflate_seek* seek, const void* d_stream, uint64_t off, uint64_t len, void* d_out, uint64_t* got,
+                                   mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_seek_read(mi355_inflate_seek* seek, uint64_t off, uint64_t len, uint8_t* out, uint64_t* got, mi355_inflate_report* report);
+int mi355_inflate_seek_read_batch_device(mi355_inflate_seek* seek, const void* d_stream, mi355_seek_range* ranges, size_t n,
+                                         mi355_inflate_report* reports /* n entries, or NULL */, void* hip_stream);
+/* A measuring aid and no part of the stable interface: what the handle's last read did, from its plan -- v[0] entries decoded, v[1]
+ * symbols stored (lead-ins included), v[2] window steps, v[3] launch sets. */
+int mi355_inflate_seek_last_read(mi355_inflate_seek* seek, uint64_t v[4]);
+
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
  * [parse_lo, parse_hi) (buffer coordinates; parse_lo = 32768 of history except on the first rank,
