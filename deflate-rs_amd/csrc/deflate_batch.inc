@@ -503,9 +503,9 @@ int batch_launch_set(mi355_deflate_ctx* c, const BatchView* v, uint32_t k, const
             hipLaunchKernelGGL(kb_nohash<false>, dim3(total(BS_RLE)), dim3(256), 0, st, a);
     } else {
         if (c->sort_mode == 1)
-            hipLaunchKernelGGL(kb_sort<1>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, c->sort_break ? 3u : 1u);
+            hipLaunchKernelGGL(kb_sort<1>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, sort_dbl(c, 1));
         else
-            hipLaunchKernelGGL(kb_sort<0>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, 1u);
+            hipLaunchKernelGGL(kb_sort<0>, dim3(total(BS_SORT)), dim3(1024), 0, st, a, sort_dbl(c, 0));
         if (has_q && single)
             MI355_BWALK(true, true);
         else if (has_q)

@@ -207,6 +207,12 @@ struct mi355_deflate_ctx {
     int sort_mode = 0;  // k_sort<MODE>: 1 once the device has passed k_lds_order_test -- ranks from returning LDS atomics -- else 0
     bool lds_order_ok = false;  // the answer of k_lds_order_test
     int sort_break = 0;         // (MI355_DEBUG_HOOKS builds: k_sort<1> mis-ranks on purpose)
+#ifdef MI355_DEBUG_HOOKS
+    int force_swz = 0;                  // mi355_debug_force_swz: 0 product, 1 every epoch with J >= 1024 marked, 2 none
+    const uint16_t* dbg_sorted = nullptr;   // the tables the last single-pass call left in the workspace (mi355_debug_sort_tables)
+    const uint16_t* dbg_buckets = nullptr;
+    uint64_t dbg_epochs = 0;
+#endif
     uint32_t last_spec_bad = 0;
     bool reuse_tables = false;  // the encode that follows is the second attempt at an input whose match table and restart steps
                                 // are still in the workspace (run_encode after a failed speculative parse)
@@ -408,6 +414,9 @@ int ensure_ws(mi355_deflate_ctx* c, size_t bytes) {
     if (bytes <= c->ws_cap) return MI355_OK;
     c->last_plan = nullptr;
     c->last_nb = 0;
+#ifdef MI355_DEBUG_HOOKS
+    c->dbg_epochs = 0;  // (the tables' memory goes away below)
+#endif
     if (c->ws) {
         (void)hipFree(c->ws);
         c->ws = nullptr;
@@ -583,14 +592,23 @@ void info_from_scalars(mi355_deflate_info* info, const DevScalars& s) {
 }
 // (bytes of the stream with its frame: stages.h stream_bytes, shared with kb_place)
 
+// the `dbl` argument of k_sort / kb_sort: bit 0 = entries as 2 * position; the further bits are read by the test build only
+// (bit 1: mi355_debug_break_sort, ranks from atomics only; bits 2 and 3: mi355_debug_force_swz)
+inline uint32_t sort_dbl(const mi355_deflate_ctx* c, int mode) {
+#ifdef MI355_DEBUG_HOOKS
+    return 1u | ((mode == 1 && c->sort_break) ? 2u : 0u) | (c->force_swz == 1 ? 4u : 0u) | (c->force_swz == 2 ? 8u : 0u);
+#else
+    return 1u | ((mode == 1 && c->sort_break) ? 2u : 0u);
+#endif
+}
 void launch_sort(mi355_deflate_ctx* c, hipStream_t st, uint32_t epochs, const uint8_t* d_in, uint32_t n32, const HashOverride& ov,
                  uint16_t* S, uint16_t* B, uint32_t e0, const SortInit* init = nullptr) {
     if (epochs == 0) return;
     const SortInit in0 = init ? *init : SortInit{nullptr, 0u, nullptr, 0u};
     if (c->sort_mode == 1)
-        hipLaunchKernelGGL(k_sort<1>, dim3(epochs), dim3(1024), 0, st, d_in, n32, ov, S, B, e0, c->sort_break ? 3u : 1u, in0);
+        hipLaunchKernelGGL(k_sort<1>, dim3(epochs), dim3(1024), 0, st, d_in, n32, ov, S, B, e0, sort_dbl(c, 1), in0);
     else
-        hipLaunchKernelGGL(k_sort<0>, dim3(epochs), dim3(1024), 0, st, d_in, n32, ov, S, B, e0, 1u, in0);
+        hipLaunchKernelGGL(k_sort<0>, dim3(epochs), dim3(1024), 0, st, d_in, n32, ov, S, B, e0, sort_dbl(c, 0), in0);
 }
 
 // The walk's plan for `n_ep` epochs: `split` workgroups per epoch (match3_split), and `single` for the launch that walks both
@@ -880,6 +898,9 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
     c->last_plan = nullptr;  // (they point into the workspace, which may move or be reused below)
     c->last_nb = 0;
     c->q1_last_on = 0;
+#ifdef MI355_DEBUG_HOOKS
+    c->dbg_epochs = 0;
+#endif
     if (c->spec_pause > 0) c->spec_pause--;
     const bool spec = c->spec_pause == 0;  // segment entries by speculation + check (k_emit<1>) instead of exit tables and tree
     const bool reuse = c->reuse_tables;    // (the match table and the restart steps of this very input are in the workspace)
@@ -914,6 +935,11 @@ int run_encode(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, const mi35
     int rc = ensure_ws(c, sz.bytes);
     if (rc) return rc;
     Workspace w = carve(c->ws, n, cfg.use_quarter, m, gz_len, n_skew + n_holes);
+#ifdef MI355_DEBUG_HOOKS
+    c->dbg_sorted = w.sorted + WINDOW_SIZE;
+    c->dbg_buckets = w.buckets;
+    c->dbg_epochs = (n + WINDOW_SIZE - 1) / WINDOW_SIZE;
+#endif
     // A small plain call (no flush points, no quirks, the sorted path from its first epoch: k_sort is its first kernel) has that
     // kernel clear the scalars and set the one segment end, and k_block_hist clear the output buffer: the runtime's fills were four
     // launches on the way of a call of seventeen (pg11.txt: 22 of 285 us).
@@ -1296,6 +1322,11 @@ int run_streamed_body(mi355_deflate_ctx* c, const uint8_t* d_in, uint64_t n, con
     int rc = ensure_ws(c, sz.bytes);
     if (rc) return rc;
     Workspace w = carve(c->ws, n, cfg.use_quarter, 1, gz_len, 0);
+#ifdef MI355_DEBUG_HOOKS
+    c->dbg_sorted = w.sorted + WINDOW_SIZE;
+    c->dbg_buckets = w.buckets;
+    c->dbg_epochs = (n + WINDOW_SIZE - 1) / WINDOW_SIZE;
+#endif
     HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.seg_ends), (int)(uint32_t)n, 1, st));
     const SegEnds sg{w.seg_ends, 1u};
     mi355_deflate_info& info = c->info;

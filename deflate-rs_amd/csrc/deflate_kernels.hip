@@ -966,6 +966,8 @@ __device__ __forceinline__ void k_sort_body(uint32_t bx_, const uint8_t* in, uin
         }
     }
     __syncthreads();
+    // (dbl bits 2 and 3; mi355_debug_force_swz: the mark below set for every epoch that may carry it, or for none)
+    const uint32_t force_swz = (dbl >> 2) & 3u;
     dbl &= 1u;
 #endif
     // Do the epoch's sorted positions sit on few LDS banks?  Four times 64 neighbours of the sorted array -- the lanes of four of
@@ -990,7 +992,11 @@ __device__ __forceinline__ void k_sort_body(uint32_t bx_, const uint8_t* in, uin
                 few += nb <= MI355_SWZ_BANKS ? 1u : 0u;
                 very += nb <= MI355_SWZ_BANKS / 2 ? 1u : 0u;
             }
-            Bg[(size_t)e * BSTRIDE + WINDOW_SIZE + 2] = (J >= 1024 && (few >= 2 || very >= 1) && dbl) ? 1 : 0;
+            bool banks_few = few >= 2 || very >= 1;
+#ifdef MI355_DEBUG_HOOKS
+            if (force_swz) banks_few = force_swz == 1u;
+#endif
+            Bg[(size_t)e * BSTRIDE + WINDOW_SIZE + 2] = (J >= 1024 && banks_few && dbl) ? 1 : 0;
         }
     }
     uint4* out = reinterpret_cast<uint4*>(Sg + (size_t)e * WINDOW_SIZE);

@@ -670,6 +670,29 @@ int mi355_debug_break_sort(mi355_deflate_ctx* c, int on) {
     return MI355_OK;
 }
 int mi355_debug_sort_ranks(mi355_deflate_ctx* c) { return c ? c->sort_mode : -1; }
+// test build only: the sort's tables of the context's last single-pass call, as they lie in its workspace -- `ne` epochs from
+// e0 on, 32 768 entries of S (2 x position) and BSTRIDE entries of B each.  (Allocations of their own: nothing behind the walk
+// writes them.)
+int mi355_debug_sort_tables(mi355_deflate_ctx* c, uint32_t e0, uint32_t ne, uint16_t* S_out, uint16_t* B_out) {
+    if (!c || (ne && (!S_out || !B_out))) return MI355_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->own_stream) != hipSuccess) return MI355_E_HIP;
+    if (!c->dbg_sorted || (uint64_t)e0 + ne > c->dbg_epochs) {
+        c->err = "the workspace holds fewer sorted epochs than asked for";
+        return MI355_E_ARG;
+    }
+    if (ne == 0) return MI355_OK;
+    if (hipMemcpy(S_out, c->dbg_sorted + (size_t)e0 * WINDOW_SIZE, (size_t)ne * WINDOW_SIZE * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(B_out, c->dbg_buckets + (size_t)e0 * BSTRIDE, (size_t)ne * BSTRIDE * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return MI355_E_HIP;
+    return MI355_OK;
+}
+// test build only: 1 = k_sort marks every epoch with 1024 or more positions for the permuted pair table (k_match3_swz) whatever
+// its samples say -- a state that data could produce --, 2 = it marks none, 0 = by the samples
+int mi355_debug_force_swz(mi355_deflate_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MI355_E_ARG;
+    c->force_swz = mode;
+    return MI355_OK;
+}
 #endif
 
 }  // extern "C"

@@ -931,6 +931,14 @@ void mi355_deflate_stream_free(mi355_deflate_stream* s);
  * a test can watch the match kernel's order check catch it.  _sort_ranks reports what the context sorts with now. */
 int mi355_debug_break_sort(mi355_deflate_ctx* ctx, int on);
 int mi355_debug_sort_ranks(mi355_deflate_ctx* ctx);
+/* The sort's tables as the context's last single-pass call left them in its workspace, copied to host memory after a wait for
+ * the context's stream: for `ne` epochs from `e0` on, 32 768 entries of S (positions by (hash, position), stored x 2; those
+ * from the epoch's J on are unspecified) and 32 776 entries of B (bucket starts, [32768] = J, [32769] = run flag, [32770] =
+ * the mark for the permuted pair table).  MI355_E_ARG if the workspace holds fewer epochs. */
+int mi355_debug_sort_tables(mi355_deflate_ctx* ctx, uint32_t e0, uint32_t ne, uint16_t* S_out, uint16_t* B_out);
+/* mode 0: the product's behaviour.  1: every epoch with J >= 1024 carries the mark, whatever its samples say (only states that
+ * input data could produce).  2: no epoch carries it. */
+int mi355_debug_force_swz(mi355_deflate_ctx* ctx, int mode);
 #endif
 
 #ifdef __cplusplus

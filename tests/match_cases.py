@@ -975,6 +975,41 @@ def check_train(tr):
     return len(tr["targets"])
 
 
+# ---- the host's rules, restated (tests/test_match_walk_gpu.py, tests/test_match_walk_swz_gpu.py) ----------------------------------------
+def plan(n_ep, n_cu):
+    """deflate_host.inc:457-471 match3_split, :568-573 walk_plan, :585 the both-tables launch -> (split, single, both)"""
+    costs = [((n_ep * s + n_cu - 1) // n_cu) * (1.35 + 16.0 / s) for s in range(1, 17)]
+    split = 1
+    for s in range(2, 17):
+        if costs[s - 1] < costs[split - 1] - 1e-9:
+            split = s
+    return split, split >= 16 and n_ep * split * 2 <= n_cu, n_ep * split <= 256
+
+
+# ---- the permuted-table form (k_match3_swz, PairWinT<true>): only an epoch of 1024 or more positions can carry k_sort's mark -------------
+SWZ_MIN_J = 1024
+
+
+def in_long_epochs(c):
+    """the targets of a case or train that lie in an epoch with 1024 or more positions that have a hash byte"""
+    n = len(c["data"])
+    return [t for t in c["targets"] if min(max(n - 2 - t["p"] // EPOCH * EPOCH, 0), EPOCH) >= SWZ_MIN_J]
+
+
+def needs_padding(c):
+    """a case of the trains' kind (not about the end of the input) with a target in a short last epoch"""
+    return in_train(c) and len(in_long_epochs(c)) < len(c["targets"])
+
+
+@functools.lru_cache(maxsize=None)
+def padded(name):
+    """the case with text behind it up to the end of its last epoch, as in a train: every target then lies in a full epoch"""
+    c = case(name)
+    fill = -len(c["data"]) % EPOCH
+    return dict(c, name="padded_" + name, family="padded", data=c["data"] + datagen.text_like(fill + 8, 903)[:fill],
+                targets=[dict(t, part=name) for t in c["targets"]])
+
+
 # ---- what a failing parity test prints -------------------------------------------------------------------------------------------------
 def _flat(stream):
     out = []

@@ -12,9 +12,8 @@ whose length selects the both-tables kernel with whole epochs and the turn-round
 with whole epochs, k_match3 in parts, and the both-tables kernel in 16 parts without SINGLE.  plan() is asserted for every train,
 so a change of the thresholds fails the test instead of emptying it.
 
-Out of scope: the permuted-table form (k_match3_swz).  Whether k_sort marks an epoch for it depends on four samples of its sorted
-array, and nothing in the ABI reports the mark, so a case embedded in records could pass without ever reaching that kernel.  A
-change that reports the mark would lift this.  pytest -m gpu."""
+The permuted-table form (k_match3_swz, PairWinT<true>) is taken for epochs that k_sort marks; tests/test_match_walk_swz_gpu.py
+runs these cases through it on the test build of the library, which can set the mark and reports it.  pytest -m gpu."""
 import os
 import sys
 import zlib
@@ -63,14 +62,7 @@ def same_stream(got, c, what):
 
 
 # ---- the host's rules, restated -------------------------------------------------------------------------------------------------------
-def plan(n_ep, n_cu):
-    """deflate_host.inc:457-471 match3_split, :568-573 walk_plan, :585 the both-tables launch -> (split, single, both)"""
-    costs = [((n_ep * s + n_cu - 1) // n_cu) * (1.35 + 16.0 / s) for s in range(1, 17)]
-    split = 1
-    for s in range(2, 17):
-        if costs[s - 1] < costs[split - 1] - 1e-9:
-            split = s
-    return split, split >= 16 and n_ep * split * 2 <= n_cu, n_ep * split <= 256
+plan = mc.plan  # (match_cases.py: shared with tests/test_match_walk_swz_gpu.py)
 
 
 def n_cu():
