@@ -244,6 +244,11 @@ struct mi355_deflate_ctx {
     hipEvent_t t_ev[4] = {};                      // between the launch kinds of a tabled inflate, when the stage clocks are on
     bool t_ev_ok = false;
     float t_ms[4] = {};                           // mi355_inflate_tabled_last_stages: decode, windows, resolve, checksums
+    uint64_t seek_cut_bytes = 0;  // MI355_CFG_INFLATE_SEEK_CUT_BYTES: output bytes between the cuts of a seek handle's entries; 0: none
+    uint64_t seek_cut_walker = 0; // MI355_CFG_INFLATE_SEEK_CUT_WALKER: 1 = the build finds the cuts in a launch of its own (measuring aid)
+    hipEvent_t sk_ev[5] = {};     // around the launches of a seek read's set, when the stage clocks are on
+    bool sk_ev_ok = false;
+    float sk_ms[4] = {};          // mi355_inflate_seek_last_read_stages: pass 1, flatten, windows, resolve
     // deflate_index_inflate.inc: the block table of a stream nobody kept one for
     uint64_t index_span = 16384;  // MI355_CFG_INFLATE_INDEX_SPAN_BYTES: compressed bytes of one span (ix::SPAN_DEFAULT)
     hipEvent_t x_ev[3] = {};      // around the two launches of an index, when the stage clocks are on
@@ -1783,6 +1788,8 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->t_dev) (void)hipFree(c->t_dev);
     if (c->t_ev_ok)
         for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->t_ev[k]);
+    if (c->sk_ev_ok)
+        for (int k = 0; k < 5; k++) (void)hipEventDestroy(c->sk_ev[k]);
     if (c->x_ev_ok)
         for (int k = 0; k < 3; k++) (void)hipEventDestroy(c->x_ev[k]);
     if (c->m_dev) (void)hipFree(c->m_dev);

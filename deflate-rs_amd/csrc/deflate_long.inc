@@ -590,6 +590,7 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
     if (key == MI355_CFG_INFLATE_INDEX_SPAN_BYTES && (value < 256 || value > (1ull << 30))) return MI355_E_ARG;
     if (key == MI355_CFG_INFLATE_MEMBER_SPAN_BYTES && (value < 16 || value > (1ull << 30))) return MI355_E_ARG;
     if (key == MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES && value && (value < 1024 || value > (1ull << 30))) return MI355_E_ARG;
+    if (key == MI355_CFG_INFLATE_SEEK_CUT_BYTES && value && (value < 64 || value > (1ull << 30))) return MI355_E_ARG;
     DefaultGuard dg_;
     c = use_ctx(c, dg_);
     if (!c) return MI355_E_HIP;
@@ -646,6 +647,13 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
     case MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES:
         c->member_parallel = value;
         return MI355_OK;
+    case MI355_CFG_INFLATE_SEEK_CUT_BYTES:
+        c->seek_cut_bytes = value;
+        return MI355_OK;
+    case MI355_CFG_INFLATE_SEEK_CUT_WALKER:
+        if (value > 1) return MI355_E_ARG;
+        c->seek_cut_walker = value;
+        return MI355_OK;
     case MI355_CFG_SORT_RANKS:
         if (value > 1) return MI355_E_ARG;
         if (value == 1 && !c->lds_order_ok) return MI355_E_UNSUPPORTED;  // the device failed the self-test
@@ -653,6 +661,17 @@ int mi355_deflate_ctx_config(mi355_deflate_ctx* c, int key, uint64_t value) {
         return MI355_OK;
     default: return MI355_E_ARG;
     }
+}
+
+// what a key of the decode side is set to (the keys 11 to 16; any other: MI355_E_ARG)
+int mi355_deflate_ctx_config_get(mi355_deflate_ctx* c, int key, uint64_t* value) {
+    if (!value || key < MI355_CFG_INFLATE_GROUP_BYTES || key > MI355_CFG_INFLATE_SEEK_CUT_WALKER) return MI355_E_ARG;
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    const uint64_t v[6] = {c->inflate_group_bytes, c->index_span, c->member_span, c->member_parallel, c->seek_cut_bytes, c->seek_cut_walker};
+    *value = v[key - MI355_CFG_INFLATE_GROUP_BYTES];
+    return MI355_OK;
 }
 
 // what a stream handle holds in host memory: gathered input, window, bytes not yet taken

@@ -10,6 +10,9 @@
 // The build is the tabled inflate's passes 1 and 2 (k_inflate_tab, k_inflate_tab_window) group by group without an output buffer; a
 // framed stream's groups are resolved into a scratch region for the checksum launches.  The host driver's shared steps are in
 // decode_host.inc.  DESIGN.md section 16.
+// With MI355_CFG_INFLATE_SEEK_CUT_BYTES set at the build, the handle also keeps CUTS inside its entries (inflate_cut.h; the kernels are
+// deflate_cut_inflate.inc's): the build's pass 1 is k_inflate_tab_cut, and a read's pass 1 is k_inflate_cut over cuts with
+// k_inflate_cut_flatten behind it -- four launches a set -- in front of the same passes 2 and 3.  DESIGN.md section 17.
 #include <memory>
 
 #include "inflate_seek.h"
@@ -108,6 +111,8 @@ __global__ __launch_bounds__(256) void k_inflate_seek_resolve(const is::Part* __
 
 }  // namespace mi355
 
+#include "deflate_cut_inflate.inc"
+
 // what a seek handle owns: the table on the host, the windows of its points on the device, and -- the host form -- the stream
 struct mi355_inflate_seek {
     mi355_deflate_ctx* c = nullptr;
@@ -119,13 +124,28 @@ struct mi355_inflate_seek {
     size_t store_bytes = 0;
     uint8_t* d_stream = nullptr;  // mi355_inflate_seek_build: the handle's own copy
     is::Counts last{0, 0, 0, 0};
+    // cuts (inflate_cut.h): entry g's are cuts[cut0[g], cut0[g + 1]); none when the handle was built with the key at 0
+    uint64_t cut_bytes = 0, cut_span = 0;  // (cut_span: the output bytes of the largest cut)
+    std::vector<icut::Cut> cuts;
+    std::vector<uint64_t> cut0;
+    icut::Counts last_cuts{0, 0, 0, 0};
 };
 
 namespace {
 
 static_assert(sizeof(is::Part) == 88 && sizeof(KeepItem) == 8, "what the kernels read");
+static_assert(sizeof(icut::Cut) == 24 && sizeof(mi355_seek_cut) == 24 && sizeof(icut::Item) == 56 && sizeof(icut::Rec) == 72, "the cuts' records");
+static_assert(icut::CUT_MIN == 64 && icut::CUT_MAX == (1ull << 30), "the range of MI355_CFG_INFLATE_SEEK_CUT_BYTES");
 static_assert(sizeof(mi355_seek_info) == 56 && sizeof(mi355_seek_point) == 16 && sizeof(mi355_seek_range) == 40, "the seek calls' records");
 static_assert(is::SPACING_DEFAULT == (1ull << 20) && is::SPACING_MIN == 32768 && is::SPACING_MAX == (1ull << 30), "the spacing's default and range");
+
+// the device room of a build's cuts, freed when the build leaves
+struct CutRoom {
+    uint8_t* p = nullptr;
+    ~CutRoom() {
+        if (p) (void)hipFree(p);
+    }
+};
 
 void seek_release(mi355_inflate_seek* h) {
     if (!h) return;
@@ -175,9 +195,26 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
         base = ents[k0].pos;
         stored = (k1 < n_blocks ? ents[k1].pos : total) - base;
     };
+    // with cuts: a group's slots -- [slot0 n + 1] [n_cut n] [Cut slots] in a room of the build's own -- are a prefix sum of the table
+    const uint64_t cb = c->seek_cut_bytes;
+    h->cut_bytes = cb;
+    const auto slots_of = [&](uint64_t k0, uint64_t k1) {
+        uint64_t sum = 0;
+        for (uint64_t k = k0; k < k1; k++) sum += icut::ict_slots(blocks[k].in_bytes, cb);
+        return sum;
+    };
+    uint64_t slots_max = 0;
     size_t ws = 0, n_max = 0;
     for (uint64_t k0 = 0, k1, base, stored; k0 < n_blocks; k0 = k1) {
         group(k0, k1, base, stored);
+        if (cb) {
+            const uint64_t sl = slots_of(k0, k1);
+            if (sl > 0xffffffffull) {
+                c->err = "inflate seek: a group has more cuts than a launch takes";
+                return MI355_E_UNSUPPORTED;
+            }
+            slots_max = sl > slots_max ? sl : slots_max;
+        }
         if (wrapper && stored > VERIFY_MAX_IN) {
             c->err = "inflate seek: a group of a framed stream is larger than the checksum kernels take";
             return MI355_E_UNSUPPORTED;
@@ -193,6 +230,14 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
     const size_t part_at = align_up(rec_at + sizeof(ic::Rec) * n_max, 256), keep_at = part_at + 256;
     rc = verify_room(c, align_up(keep_at + sizeof(KeepItem) * n_max, 256) + 512);
     if (rc) return rc;
+    CutRoom room;
+    const size_t ncut_at = align_up(sizeof(uint64_t) * (n_max + 1), 256), slot_at = align_up(ncut_at + sizeof(uint32_t) * n_max, 256);
+    std::vector<uint8_t> cut_host;
+    if (cb) {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&room.p), slot_at + sizeof(icut::Cut) * slots_max + 256));
+        cut_host.resize(slot_at + sizeof(icut::Cut) * slots_max);
+        h->cut0.assign(1, 0);
+    }
     iw::Rec acc = iw::Rec{ic::V_OK, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t adler = 1, crc = 0;
     size_t next_pt = 1;  // (point 0 has no window to keep)
@@ -217,7 +262,23 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
         HIPCHK(c, hipMemcpyAsync(c->v_dev + part_at, c->v_host + part_at, keep_at + sizeof(KeepItem) * n_keep - part_at, hipMemcpyHostToDevice, st));
         if (first) HIPCHK(c, hipMemsetAsync(c->t_dev, 0, it::WIN, st));  // (nothing refers to the window in front of the stream)
         first = false;
-        hipLaunchKernelGGL(k_inflate_tab, dim3(n), dim3(64), 0, st, item, d_ents, d_recs);
+        uint64_t n_slots = 0;
+        if (cb) {
+            uint64_t* slot0 = reinterpret_cast<uint64_t*>(cut_host.data());
+            for (uint32_t k = 0; k < n; k++) slot0[k] = n_slots, n_slots += icut::ict_slots(blocks[k0 + k].in_bytes, cb);
+            slot0[n] = n_slots;
+            HIPCHK(c, hipMemcpyAsync(room.p, slot0, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, st));
+            TItem walk = item;
+            if (c->seek_cut_walker) {  // (the alternative the bench measures: pass 1 as without cuts, then a walk that stores no symbol)
+                hipLaunchKernelGGL(k_inflate_tab, dim3(n), dim3(64), 0, st, item, d_ents, d_recs);
+                HIPCHK(c, hipGetLastError());
+                walk.cap = walk.base;
+            }
+            hipLaunchKernelGGL(k_inflate_tab_cut, dim3(n), dim3(64), 0, st, walk, d_ents, d_recs, reinterpret_cast<const uint64_t*>(room.p),
+                               reinterpret_cast<icut::Cut*>(room.p + slot_at), reinterpret_cast<uint32_t*>(room.p + ncut_at), cb);
+        } else {
+            hipLaunchKernelGGL(k_inflate_tab, dim3(n), dim3(64), 0, st, item, d_ents, d_recs);
+        }
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_inflate_tab_window, dim3(1), dim3(1024), 0, st, item, d_ents, d_recs, d_lim);
         HIPCHK(c, hipGetLastError());
@@ -237,8 +298,19 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
         // the group's last window stays on the device as the window in front of the next group
         if (k1 < n_blocks) HIPCHK(c, hipMemcpyAsync(c->t_dev, c->t_dev + (size_t)n * it::WIN, it::WIN, hipMemcpyDeviceToDevice, st));
         HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(ic::Rec) * n, hipMemcpyDeviceToHost, st));
+        if (cb)
+            HIPCHK(c, hipMemcpyAsync(cut_host.data() + ncut_at, room.p + ncut_at, slot_at - ncut_at + sizeof(icut::Cut) * n_slots, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));  // the one wait of a group
         if (!it::it_report(reinterpret_cast<const ic::Rec*>(c->v_host + rec_at), n, acc)) break;
+        if (cb) {  // the slots an entry filled, packed behind those of the entries in front of it
+            const uint64_t* slot0 = reinterpret_cast<const uint64_t*>(cut_host.data());
+            const uint32_t* n_cut = reinterpret_cast<const uint32_t*>(cut_host.data() + ncut_at);
+            const icut::Cut* slots = reinterpret_cast<const icut::Cut*>(cut_host.data() + slot_at);
+            for (uint32_t k = 0; k < n; k++) {
+                h->cuts.insert(h->cuts.end(), slots + slot0[k], slots + slot0[k] + n_cut[k]);
+                h->cut0.push_back(h->cuts.size());
+            }
+        }
         if (wrapper && stored) {
             adler = mi355_checksum_combine(1, adler, c->h_sc->adler, stored);
             crc = mi355_checksum_combine(2, crc, c->h_sc->crc, stored);
@@ -259,12 +331,18 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
         inflate_say(c, *report, rc, "inflate seek");
         return rc;
     }
+    for (size_t g = 0; g + 1 < h->cut0.size(); g++)
+        for (uint64_t i = h->cut0[g]; i < h->cut0[g + 1]; i++) {
+            const uint64_t end = i + 1 < h->cut0[g + 1] ? h->cuts[i + 1].pos : (g + 1 < n_blocks ? ents[g + 1].pos : total);
+            h->cut_span = end - h->cuts[i].pos > h->cut_span ? end - h->cuts[i].pos : h->cut_span;
+        }
     *out = h.release();
     return MI355_OK;
 }
 
 // A batch of ranges, device resident stream and buffers (the entry has checked the arguments): the plan, then pass 1, 2 and 3 per
-// launch set, one wait a set.
+// launch set, one wait a set.  A handle with cuts differs in its descriptors, in the kernel of pass 1 and in the flatten launch
+// behind it; everything else of a set is the same text.
 int seek_read_ranges(mi355_inflate_seek* h, mi355_deflate_ctx* c, const uint8_t* d_stream, mi355_seek_range* r, size_t n,
                      mi355_inflate_report* reports, hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -275,35 +353,77 @@ int seek_read_ranges(mi355_inflate_seek* h, mi355_deflate_ctx* c, const uint8_t*
                 h->last);
     std::vector<iw::Rec> acc(n, iw::Rec{ic::V_OK, 0, 0, 0, 0, 0, 0, 0, 0});
     std::vector<uint8_t> failed(n, 0);
+    const bool cut = h->cut_bytes != 0;
+    h->last_cuts = icut::Counts{0, h->last.symbols, 0, 0};
+    std::vector<icut::Item> items;
+    std::vector<uint32_t> item0;
+    std::vector<uint64_t> ent0;
+    // (a measuring aid, only when asked: the time per launch kind -- pass 1, flatten, windows, resolve -- summed over the sets)
+    StageClocks<4, 5> clk{c->sk_ev, c->sk_ev_ok, c->sk_ms, st, stage_clocks_on(c, h->last.symbols)};
+    if (const int rc = clk.begin(c)) return rc;
     for (is::Set& s : sets) {
         is::is_drop(s, failed);
         const size_t np = s.parts.size(), ne = s.ents.size();
         if (ne > 0x7fffffffull) return MI355_E_UNSUPPORTED;
-        // workspace: [window slots] [symbols]; descriptors: [Part np] [Entry ne] | [limit np] [Rec ne]
+        if (cut) {  // the set's cuts: pass 1 runs over them, and flatten stands between it and pass 2
+            ent0.resize(np);
+            for (size_t j = 0; j < np; j++) ent0[j] = h->pts[is::is_point_of(h->ents.data(), h->pts, s.parts[j].lo)];
+            icut::ict_items(s, ent0, h->cut0, h->cuts, items, item0);
+            if (items.size() > 0x7fffffffull) return MI355_E_UNSUPPORTED;
+            h->last_cuts.cuts += items.size(), h->last_cuts.steps += items.size() - ne;
+        }
+        const size_t ni = cut ? items.size() : 0;
+        h->last_cuts.launches += cut ? 4 : 3;
+        // workspace: [window slots] [symbols]; descriptors: [Part np] [Entry ne] ([Item ni] [first ne + 1]) | [limit np] [Rec ne] ([cut Rec ni])
         const size_t sym_at = (size_t)s.slots * it::WIN;
         int rc = ensure_buf(c, &c->t_dev, &c->t_dev_cap, sym_at + 2 * (size_t)s.syms + 256);
         if (rc) return rc;
-        const size_t ent_at = align_up(sizeof(is::Part) * np, 256), lim_at = align_up(ent_at + sizeof(ic::Entry) * ne, 256);
-        const size_t rec_at = align_up(lim_at + sizeof(uint64_t) * np, 256);
-        rc = verify_room(c, rec_at + sizeof(ic::Rec) * ne + 256);
+        const size_t ent_at = align_up(sizeof(is::Part) * np, 256), item_at = align_up(ent_at + sizeof(ic::Entry) * ne, 256);
+        const size_t first_at = align_up(item_at + sizeof(icut::Item) * ni, 256);
+        const size_t front = cut ? first_at + sizeof(uint32_t) * (ne + 1) : ent_at + sizeof(ic::Entry) * ne;  // what goes to the device
+        const size_t lim_at = align_up(front, 256), rec_at = align_up(lim_at + sizeof(uint64_t) * np, 256);
+        const size_t crec_at = align_up(rec_at + sizeof(ic::Rec) * ne, 256);
+        rc = verify_room(c, crec_at + sizeof(icut::Rec) * ni + 256);
         if (rc) return rc;
         memcpy(c->v_host, s.parts.data(), sizeof(is::Part) * np);
         memcpy(c->v_host + ent_at, s.ents.data(), sizeof(ic::Entry) * ne);
+        if (cut) {
+            memcpy(c->v_host + item_at, items.data(), sizeof(icut::Item) * ni);
+            memcpy(c->v_host + first_at, item0.data(), sizeof(uint32_t) * (ne + 1));
+        }
         const is::Part* d_parts = reinterpret_cast<const is::Part*>(c->v_dev);
         const ic::Entry* d_ents = reinterpret_cast<const ic::Entry*>(c->v_dev + ent_at);
         uint64_t* d_lim = reinterpret_cast<uint64_t*>(c->v_dev + lim_at);
         ic::Rec* d_recs = reinterpret_cast<ic::Rec*>(c->v_dev + rec_at);
         uint16_t* d_sym = reinterpret_cast<uint16_t*>(c->t_dev + sym_at);
-        HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, ent_at + sizeof(ic::Entry) * ne, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_inflate_seek, dim3((uint32_t)ne), dim3(64), 0, st, d_parts, d_ents, d_sym, d_recs);
+        HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, front, hipMemcpyHostToDevice, st));
+        HIPCHK(c, clk.mark(0));
+        if (cut) {
+            const icut::Item* d_items = reinterpret_cast<const icut::Item*>(c->v_dev + item_at);
+            icut::Rec* d_crecs = reinterpret_cast<icut::Rec*>(c->v_dev + crec_at);
+            hipLaunchKernelGGL(k_inflate_cut, dim3((uint32_t)ni), dim3(64), 0, st, d_parts, d_ents, d_items, d_sym, d_crecs);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, clk.mark(1));
+            hipLaunchKernelGGL(k_inflate_cut_flatten, dim3((uint32_t)ne), dim3(1024), 0, st, d_parts, d_ents, d_items,
+                               reinterpret_cast<const uint32_t*>(c->v_dev + first_at), d_crecs, d_sym, d_recs);
+        } else {
+            hipLaunchKernelGGL(k_inflate_seek, dim3((uint32_t)ne), dim3(64), 0, st, d_parts, d_ents, d_sym, d_recs);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, clk.mark(1));
+        }
         HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.mark(2));
         hipLaunchKernelGGL(k_inflate_seek_window, dim3((uint32_t)np), dim3(1024), 0, st, d_parts, d_ents, d_recs, d_sym, h->store, c->t_dev, d_lim);
         HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.mark(3));
         hipLaunchKernelGGL(k_inflate_seek_resolve, dim3(cdiv(s.syms, 256 * it::RESOLVE_RUN)), dim3(256), 0, st, d_parts, (uint32_t)np, d_ents, d_lim,
                            d_sym, c->t_dev, s.syms);
         HIPCHK(c, hipGetLastError());
+        HIPCHK(c, clk.mark(4));
         HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(ic::Rec) * ne, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));  // the one wait of a set
+        clk.lap(0, 1, 0), clk.lap(2, 3, 2), clk.lap(3, 4, 3);
+        if (cut) clk.lap(1, 2, 1);  // (without cuts the two marks stand back to back: no launch kind's time)
         const ic::Rec* recs = reinterpret_cast<const ic::Rec*>(c->v_host + rec_at);
         for (const is::Part& pt : s.parts)
             if (!failed[pt.range] && !is::is_report(recs, pt, acc[pt.range])) failed[pt.range] = 1;
@@ -433,6 +553,39 @@ int mi355_inflate_seek_read(mi355_inflate_seek* h, uint64_t off, uint64_t len, u
     if (r.got) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)r.got, hipMemcpyDeviceToHost));
     *got = r.got;
     return rc;
+}
+
+int mi355_inflate_seek_cuts(mi355_inflate_seek* h, mi355_seek_cut* out, size_t cap, size_t* n) {
+    if (!h || !n || (!out && cap)) return MI355_E_ARG;
+    *n = h->cuts.size();
+    if (*n > cap) return MI355_E_OUT_TOO_SMALL;
+    for (size_t i = 0; i < h->cuts.size(); i++) out[i] = mi355_seek_cut{h->cuts[i].bit, h->cuts[i].pos, h->cuts[i].hdr_bit};
+    return MI355_OK;
+}
+
+// the cut_bytes in force, the cuts, the host bytes they take, the output bytes of the largest cut
+int mi355_inflate_seek_cut_info(mi355_inflate_seek* h, uint64_t v[4]) {
+    if (!h || !v) return MI355_E_ARG;
+    v[0] = h->cut_bytes, v[1] = h->cuts.size(), v[2] = sizeof(icut::Cut) * h->cuts.size() + sizeof(uint64_t) * h->cut0.size(), v[3] = h->cut_span;
+    return MI355_OK;
+}
+
+// what the handle's last read did: cuts decoded, symbols stored, cuts flatten rewrote, launches
+int mi355_inflate_seek_last_read_cuts(mi355_inflate_seek* h, uint64_t v[4]) {
+    if (!h || !v) return MI355_E_ARG;
+    v[0] = h->last_cuts.cuts, v[1] = h->last_cuts.symbols, v[2] = h->last_cuts.steps, v[3] = h->last_cuts.launches;
+    return MI355_OK;
+}
+
+// HIP-event time per launch kind of the context's last seek read, summed over its sets: pass 1 (entries or cuts), flatten, windows,
+// resolve; zeros unless the stage clocks were on (MI355_CFG_STAGE_CLOCKS)
+int mi355_inflate_seek_last_read_stages(mi355_deflate_ctx* c, float ms[4]) {
+    if (!ms) return MI355_E_ARG;
+    DefaultGuard dg_;
+    c = use_ctx(c, dg_);
+    if (!c) return MI355_E_HIP;
+    for (int k = 0; k < 4; k++) ms[k] = c->sk_ms[k];
+    return MI355_OK;
 }
 
 // what the handle's last read did, from its plan: entries decoded, symbols stored, window steps, launch sets

@@ -199,6 +199,11 @@ class SeekPoint(C.Structure):
     _fields_ = [("bit", C.c_uint64), ("pos", C.c_uint64)]
 
 
+class SeekCut(C.Structure):
+    """mi355_seek_cut (24 bytes): where decoding resumes, the output position there, the header bit of the block it lies in"""
+    _fields_ = [("bit", C.c_uint64), ("pos", C.c_uint64), ("hdr_bit", C.c_uint64)]
+
+
 class SeekRange(C.Structure):
     """mi355_seek_range (40 bytes): one range of mi355_inflate_seek_read_batch_device"""
     _fields_ = [("off", C.c_uint64), ("len", C.c_uint64), ("out", C.c_void_p), ("got", C.c_uint64), ("status", C.c_int32),
@@ -359,6 +364,11 @@ def load():
     L.mi355_inflate_seek_read_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SeekRange), C.c_size_t, C.POINTER(InflateReport),
                                                        C.c_void_p]
     L.mi355_inflate_seek_last_read.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mi355_inflate_seek_cuts.argtypes = [C.c_void_p, C.POINTER(SeekCut), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_inflate_seek_cut_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mi355_inflate_seek_last_read_cuts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mi355_inflate_seek_last_read_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_deflate_ctx_config_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -393,7 +403,8 @@ EXPORTED = [
     "mi355_inflate_members_last_walks", "mi355_inflate_members_last_parallel", "mi355_inflate_members_last_parallel_stages",
     "mi355_inflate_seek_build", "mi355_inflate_seek_build_device", "mi355_inflate_seek_free", "mi355_inflate_seek_info",
     "mi355_inflate_seek_points", "mi355_inflate_seek_read", "mi355_inflate_seek_read_device", "mi355_inflate_seek_read_batch_device",
-    "mi355_inflate_seek_last_read",
+    "mi355_inflate_seek_last_read", "mi355_inflate_seek_cuts", "mi355_inflate_seek_cut_info", "mi355_inflate_seek_last_read_cuts",
+    "mi355_inflate_seek_last_read_stages", "mi355_deflate_ctx_config_get",
 ]
 
 
@@ -447,6 +458,32 @@ class SeekIndex:
         if rc != OK:
             raise DeflateError(rc, "inflate seek: bad handle")
         return dict(zip(("entries", "symbols", "steps", "sets"), v))
+
+    def cuts(self):
+        """mi355_inflate_seek_cuts: [(bit, pos, hdr_bit)] in stream order; none when the handle was built without cuts"""
+        n = C.c_size_t(0)
+        load().mi355_inflate_seek_cuts(self._h, None, 0, C.byref(n))
+        arr = (SeekCut * max(n.value, 1))()
+        rc = load().mi355_inflate_seek_cuts(self._h, arr, n.value, C.byref(n))
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return [(arr[k].bit, arr[k].pos, arr[k].hdr_bit) for k in range(n.value)]
+
+    def cut_info(self):
+        """mi355_inflate_seek_cut_info"""
+        v = (C.c_uint64 * 4)()
+        rc = load().mi355_inflate_seek_cut_info(self._h, v)
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return dict(zip(("cut_bytes", "n_cuts", "host_bytes", "largest_cut"), v))
+
+    def last_read_cuts(self):
+        """mi355_inflate_seek_last_read_cuts: what the last read did"""
+        v = (C.c_uint64 * 4)()
+        rc = load().mi355_inflate_seek_last_read_cuts(self._h, v)
+        if rc != OK:
+            raise DeflateError(rc, "inflate seek: bad handle")
+        return dict(zip(("cuts", "symbols", "steps", "launches"), v))
 
     def read_raw(self, off, length):
         """mi355_inflate_seek_read on a handle of Context.inflate_seek: (rc, report dict, the bytes that hold data); rc is OK or E_DATA"""
@@ -538,6 +575,8 @@ class Context:
     CFG_INFLATE_INDEX_SPAN_BYTES = 12
     CFG_INFLATE_MEMBER_SPAN_BYTES = 13
     CFG_INFLATE_MEMBER_PARALLEL_BYTES = 14
+    CFG_INFLATE_SEEK_CUT_BYTES = 15
+    CFG_INFLATE_SEEK_CUT_WALKER = 16
     HOST_PATH_PIECES, HOST_PATH_IN_THREADS, HOST_PATH_OUT_THREADS = 1, 2, 4
 
     def config(self, key, value):
@@ -545,6 +584,14 @@ class Context:
         rc = load().mi355_deflate_ctx_config(self._h, int(key), int(value))
         if rc != OK:
             self._err(rc)
+
+    def config_get(self, key):
+        """mi355_deflate_ctx_config_get: what a key of the decode side (11 to 16) is set to"""
+        v = C.c_uint64(0)
+        rc = load().mi355_deflate_ctx_config_get(self._h, int(key), C.byref(v))
+        if rc != OK:
+            self._err(rc)
+        return v.value
 
     def reserve(self, in_len, host_api=False):
         """mi355_deflate_ctx_reserve: allocate for inputs of up to in_len bytes now"""
@@ -820,25 +867,41 @@ class Context:
         return self._packed_result(arena, ap, items, n, used.value, rc, check)
 
     # ---- seek points: byte ranges of one large stream (mi355_inflate_seek_*) ----
-    def _seek(self, call):
+    def _seek(self, call, cut):
         h, r = C.c_void_p(), InflateReport()
-        rc = call(C.byref(h), C.byref(r))
+        if cut is not None:
+            before = self.config_get(self.CFG_INFLATE_SEEK_CUT_BYTES)
+            self.config(self.CFG_INFLATE_SEEK_CUT_BYTES, cut)  # the key is read at the build: set for it, the value before put back
+        try:
+            rc = call(C.byref(h), C.byref(r))
+        finally:
+            if cut is not None:
+                self.config(self.CFG_INFLATE_SEEK_CUT_BYTES, before)
         if rc != OK:
             self._err(rc)
         return SeekIndex(self, h, r.as_dict())
 
-    def inflate_seek(self, stream, wrapper=0, spacing=0, blocks=None):
+    def inflate_seek(self, stream, wrapper=0, spacing=0, blocks=None, cut=0):
         """mi355_inflate_seek_build on host bytes -> SeekIndex.  spacing: output bytes between points, 0 = 1 MiB; blocks: the stream's
-        table (Context.blocks()), else the device finds one.  A stream that does not decode raises DeflateError(E_DATA, ...)."""
+        table (Context.blocks()), else the device finds one.  cut: CFG_INFLATE_SEEK_CUT_BYTES for this build, the context's value put
+        back behind it (0: no cuts; None: the key is left as the context has it).  A stream that does not decode raises DeflateError(E_DATA, ...)."""
         arr, nb = self._block_table(blocks)
         stream = bytes(stream)
-        return self._seek(lambda h, r: load().mi355_inflate_seek_build(self._h, stream, len(stream), wrapper, arr, nb, spacing, h, r))
+        return self._seek(lambda h, r: load().mi355_inflate_seek_build(self._h, stream, len(stream), wrapper, arr, nb, spacing, h, r), cut)
 
-    def inflate_seek_device(self, d_stream_ptr, stream_len, wrapper=0, spacing=0, blocks=None, stream=0):
+    def inflate_seek_last_read_stages(self):
+        """mi355_inflate_seek_last_read_stages: ms per launch kind of the last seek read (zeros unless CFG_STAGE_CLOCKS was on)"""
+        v = (C.c_float * 4)()
+        rc = load().mi355_inflate_seek_last_read_stages(self._h, v)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("pass1", "flatten", "windows", "resolve"), v))
+
+    def inflate_seek_device(self, d_stream_ptr, stream_len, wrapper=0, spacing=0, blocks=None, stream=0, cut=0):
         """mi355_inflate_seek_build_device: the same for a stream in device memory, which the handle does not keep"""
         arr, nb = self._block_table(blocks)
         return self._seek(lambda h, r: load().mi355_inflate_seek_build_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, arr, nb,
-                                                                             spacing, h, r, C.c_void_p(stream)))
+                                                                             spacing, h, r, C.c_void_p(stream)), cut)
 
     # ---- verify: does the stream inflate to the input? (mi355_deflate_verify*) ----
     @staticmethod

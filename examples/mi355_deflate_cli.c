@@ -3,7 +3,7 @@
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
  *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
  *   mi355_deflate_cli -d --members [-gzip] IN OUT
- *   mi355_deflate_cli -d --range OFF:LEN [-raw|-zlib|-gzip] IN OUT
+ *   mi355_deflate_cli -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
  * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
@@ -14,7 +14,9 @@
  * BGZF, `cat a.gz b.gz` -- and the two calls are mi355_inflate_members (plain -d -gzip takes exactly one member); --members with -raw or -zlib is refused with the usage text.
  * With --range OFF:LEN only the bytes [OFF, OFF + LEN) of what IN inflates to are written (fewer at its end, like pread): a seek index
  * is built (mi355_inflate_seek_build: the table found on the GPU, a window kept every MiB of output) and the range is decoded from the
- * nearest point (mi355_inflate_seek_read); not together with --parallel or --members.
+ * nearest point (mi355_inflate_seek_read); not together with --parallel or --members.  With --cut BYTES the index also remembers
+ * a cut every BYTES of output inside its table entries (MI355_CFG_INFLATE_SEEK_CUT_BYTES: 64 bytes to 1 GiB) and the read decodes a
+ * wave per cut; only together with --range.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
  *             -Wl,-rpath,$PWD/deflate-rs_amd -o /tmp/mi355_deflate_cli */
 #include <stdio.h>
@@ -32,7 +34,8 @@ int main(int argc, char** argv) {
     int wrapper = 0, level = 1;
     size_t chunk = 0;
     int verify = 0, decompress = 0, parallel = 0, members = 0, format_given = 0, ranged = 0;
-    unsigned long long r_off = 0, r_len = 0;
+    unsigned long long r_off = 0, r_len = 0, cut = 0;
+    int cut_given = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "-raw")) wrapper = 0, format_given = 1;
@@ -54,13 +57,17 @@ int main(int argc, char** argv) {
                 r_len = strtoull(tail, &end, 10);
                 if (*end) ranged = -1;
             }
+        } else if ((!strcmp(argv[a], "--cut") || !strcmp(argv[a], "-cut")) && a + 1 < argc) {
+            char* end = NULL;
+            cut = strtoull(argv[++a], &end, 10);
+            cut_given = end && end != argv[a] && !*end ? 1 : -1;
         } else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
     /* --members is gzip by definition: another format switch beside it is refused, not ignored */
     if (argc - a != 2 || ((parallel || members || ranged) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2) ||
-        ranged < 0 || (ranged && (parallel || members))) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [-raw|-zlib|-gzip] IN OUT\n",
+        ranged < 0 || (ranged && (parallel || members)) || cut_given < 0 || (cut_given && !ranged)) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
                 argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
@@ -106,10 +113,15 @@ int main(int argc, char** argv) {
         mi355_inflate_report r;
         mi355_inflate_seek* seek = NULL;
         mi355_seek_info si;
-        uint64_t got = 0;
+        uint64_t got = 0, cv[4] = {0, 0, 0, 0};
+        if (cut_given) {
+            rc = mi355_deflate_ctx_config(ctx, MI355_CFG_INFLATE_SEEK_CUT_BYTES, cut);
+            if (rc) return fail("--cut: 0, or 64 bytes to 1 GiB", rc, NULL);
+        }
         rc = mi355_inflate_seek_build(ctx, in, n, wrapper, NULL, 0, 0, &seek, &r);
         const float build_ms = r.ms;
         if (rc == MI355_OK) rc = mi355_inflate_seek_info(seek, &si);
+        if (rc == MI355_OK) rc = mi355_inflate_seek_cut_info(seek, cv);
         uint8_t* data = NULL;
         if (rc == MI355_OK) {
             if (r_off > si.total) r_off = si.total;
@@ -127,9 +139,9 @@ int main(int argc, char** argv) {
         f = fopen(argv[a + 1], "wb");
         if (!f || fwrite(data, 1, (size_t)got, f) != (size_t)got) return fail("write output", -1, NULL);
         fclose(f);
-        fprintf(stderr, "%lu -> bytes [%llu, %llu) of %llu, %llu entries, %llu points, index %.3f ms, read %.3f ms\n", (unsigned long)n, r_off,
-                r_off + (unsigned long long)got, (unsigned long long)si.total, (unsigned long long)si.n_entries, (unsigned long long)si.n_points,
-                build_ms, r.ms);
+        fprintf(stderr, "%lu -> bytes [%llu, %llu) of %llu, %llu entries, %llu points, %llu cuts, index %.3f ms, read %.3f ms\n", (unsigned long)n,
+                r_off, r_off + (unsigned long long)got, (unsigned long long)si.total, (unsigned long long)si.n_entries,
+                (unsigned long long)si.n_points, (unsigned long long)cv[1], build_ms, r.ms);
         free(data);
         free(in);
         mi355_inflate_seek_free(seek);

@@ -179,7 +179,16 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
  *                          inflate_members_bench.json; 100 MB of text as 64 members): finding a member costs about 29 ms whatever
  *                          its size, so the path wins where one wave would need longer for the member -- deflated text: 2354 ms
  *                          on, 17 285 ms off -- and LOSES where one wave is fast -- the same members as stored blocks: 1450 ms on,
- *                          72.7 ms off.  Set 0 for files of stored or hardly compressed members. */
+ *                          72.7 ms off.  Set 0 for files of stored or hardly compressed members.
+ *   MI355_CFG_INFLATE_SEEK_CUT_BYTES  output bytes between the CUTS a seek handle remembers inside its table entries (default 0: no
+ *                          cuts, every seek call does what it did without the key; else 64 bytes .. 1 GiB, anything else is
+ *                          MI355_E_ARG).  Read when a handle is built (mi355_inflate_seek_build[_device]): the handle keeps the value
+ *                          in force.  With cuts a read decodes one wave per cut instead of one per entry.  Same bytes either way.
+ *                          The sweep of tools/inflate_cut_bench.py (profiles/inflate_cut_bench.json) favours 4 KiB on deflated text; the
+ *                          default stays 0 until turning it on is a change of its own.
+ *   MI355_CFG_INFLATE_SEEK_CUT_WALKER  a measuring aid and no part of the stable interface (default 0; 0 or 1): 1 = a build with
+ *                          cuts runs its pass 1 as without cuts and finds the cuts in a second launch that stores no symbol -- the
+ *                          alternative tools/inflate_cut_bench.py times against recording them in pass 1.  Same handle either way. */
 #define MI355_CFG_RANGE_BYTES 1
 #define MI355_CFG_LONG_FROM 2
 #define MI355_CFG_SORT_RANKS 3
@@ -194,7 +203,11 @@ const char* mi355_deflate_last_error(mi355_deflate_ctx* ctx);
 #define MI355_CFG_INFLATE_INDEX_SPAN_BYTES 12
 #define MI355_CFG_INFLATE_MEMBER_SPAN_BYTES 13
 #define MI355_CFG_INFLATE_MEMBER_PARALLEL_BYTES 14
+#define MI355_CFG_INFLATE_SEEK_CUT_BYTES 15
+#define MI355_CFG_INFLATE_SEEK_CUT_WALKER 16
 int mi355_deflate_ctx_config(mi355_deflate_ctx* ctx, int key, uint64_t value);
+/* What a key of the decode side (11 to 16) is set to; any other key is MI355_E_ARG. */
+int mi355_deflate_ctx_config_get(mi355_deflate_ctx* ctx, int key, uint64_t* value);
 
 /* deflate_bytes_conf / deflate_bytes_zlib_conf (src/lib.rs:137-147, 182-198): host buffers
  * in, host buffer out.  ctx may be NULL (the default context, see above).  An input of 16 MiB or more is
@@ -738,6 +751,35 @@ int mi355_inflate_seek_read_batch_device(mi355_inflate_seek* seek, const void* d
 /* A measuring aid and no part of the stable interface: what the handle's last read did, from its plan -- v[0] entries decoded, v[1]
  * symbols stored (lead-ins included), v[2] window steps, v[3] launch sets. */
 int mi355_inflate_seek_last_read(mi355_inflate_seek* seek, uint64_t v[4]);
+/* CUTS (MI355_CFG_INFLATE_SEEK_CUT_BYTES at the build).  A table entry begins at a block header, so a read costs
+ * what one wave needs for the blocks of the entries it touches, and a stream of fixed or stored blocks is ONE entry.  With the key set
+ * the build's walk remembers places INSIDE the entries where a wave may begin: a cut is (bit, pos, hdr_bit) -- where decoding resumes,
+ * the output position there, and the bit of the 3-bit header of the block it lies in; bit == hdr_bit: the cut stands at a block
+ * header, otherwise at a token start of a fixed or dynamic block, whose header the wave parses again for its tables.  Rule: the first
+ * cut of an entry is its start; the walk records a cut at every block header and token start whose output position lies cut_bytes
+ * or more behind the entry's last cut.  The handle keeps 24 bytes per cut on the host.  Points stay entries.
+ * A read of such a handle is four launches and one wait a set: a wave per cut from the point's entry through the cut that holds the
+ * range's last byte, a pass that makes every entry's symbols what one wave would have left and checks that each cut ended where and
+ * in the block its successor begins, then the window and resolve passes as without cuts.  Bytes, got and status of a stream that
+ * decodes as it did at the build are those of a handle without cuts; the report's block counts are those of the cuts decoded.
+ * Otherwise: MI355_E_DATA, the report is the first failing cut's in stream order (a cut that does not meet its successor:
+ * MI355_VERIFY_TABLE), nothing is stored at or beyond it, and nothing ever at or beyond out + len.  The build's status, report and
+ * points do not depend on the key.
+ * _cuts: the cuts in stream order (cap too small: MI355_E_OUT_TOO_SMALL and *n); none when the handle was built with the key at 0.
+ * _cut_info: v[0] the cut_bytes in force, v[1] cuts, v[2] host bytes they take, v[3] the output bytes of the largest cut.
+ * _last_read_cuts, a measuring aid like _last_read: v[0] cuts decoded, v[1] symbols stored, v[2] cuts the flatten pass rewrote (those
+ * behind their entry's first), v[3] kernel launches. */
+typedef struct {
+    uint64_t bit;     /* raw-deflate bit offset where decoding resumes */
+    uint64_t pos;     /* the output position there */
+    uint64_t hdr_bit; /* the header bit of the block it lies in; == bit: at a block header */
+} mi355_seek_cut; /* 24 bytes */
+int mi355_inflate_seek_cuts(mi355_inflate_seek* seek, mi355_seek_cut* out, size_t cap, size_t* n);
+int mi355_inflate_seek_cut_info(mi355_inflate_seek* seek, uint64_t v[4]);
+int mi355_inflate_seek_last_read_cuts(mi355_inflate_seek* seek, uint64_t v[4]);
+/* A measuring aid: HIP-event milliseconds per launch kind of the context's last seek read, summed over its sets -- pass 1 (entries, or
+ * cuts), flatten (0 without cuts), windows, resolve; zeros unless the stage clocks were on for the call (MI355_CFG_STAGE_CLOCKS). */
+int mi355_inflate_seek_last_read_stages(mi355_deflate_ctx* ctx, float ms[4]);
 
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
