@@ -578,8 +578,11 @@ int mi355_shard_pack(mi355_shard* s, const mi355_block_info* plans, uint64_t end
     }
     BlockPlan* const hp = s->h_plan;  // (free again: every call of this function ends in a wait for the stream)
     for (uint32_t b = 0; b < s->nb2; b++) {
-        // only a Stored block needs its raw bytes; those of a straddling block lie in the look-ahead
-        if (plans[b].btype == BT_STORED && s->h_bstart[b + 1] > s->n_ext) {
+        // only a Stored block needs its raw bytes; those of a straddling block lie in the look-ahead -- a window further on where
+        // the reference's bytes are asked for (A.4 Q13: body_k_pack.inc reads them there; the flags are those mi355_shard_blocks_ex
+        // left in h_costs)
+        const uint64_t ahead = (s->h_costs[b].q13 && (s->opts.compat & MI355_COMPAT_Q13)) ? WINDOW_SIZE : 0;
+        if (plans[b].btype == BT_STORED && (uint64_t)s->h_bstart[b + 1] + ahead > s->n_ext) {
             c->err = "a stored block of this rank reaches past the look-ahead it was given";
             return MI355_E_ARG;
         }

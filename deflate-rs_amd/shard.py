@@ -73,13 +73,35 @@ BLOCK_TOKENS = 31744
 ZONE = 576
 
 
+SEG = 1024               # a range begins on a segment of the parse (mi355_shard_begin)
+
+
+def layout_of(a, b, total, g_lo=None, g_hi=None):
+    """The layout of a rank whose range is [a, b) of `total` bytes -> dict(a, b; g_lo, g_hi: the bytes it must hold; lo, hi: a, b
+    in buffer coordinates).  By default one window of history in front of the range, rounded down to a whole window (the window
+    geometry of the rank's buffer must be the stream's), and the look-ahead behind it."""
+    if g_lo is None:
+        g_lo = max(0, (a - HISTORY) // HISTORY * HISTORY)
+    if g_hi is None:
+        g_hi = min(total, b + LOOKAHEAD)
+    return dict(a=a, b=b, g_lo=g_lo, g_hi=g_hi, lo=a - g_lo, hi=b - g_lo)
+
+
 def p1_layout(total, rank, world):
     """-> dict(a, b: the rank's byte range; g_lo, g_hi: the bytes it must hold; lo, hi: a, b in buffer
-    coordinates)."""
-    a, b = shard_range(total, rank, world)
-    g_lo = max(0, a - HISTORY)
-    g_hi = min(total, b + LOOKAHEAD)
-    return dict(a=a, b=b, g_lo=g_lo, g_hi=g_hi, lo=a - g_lo, hi=b - g_lo)
+    coordinates).  The ranges are shard_range's, multiples of 32 KiB, while every rank gets at least that much.  A smaller input
+    is cut at multiples of 1024 bytes -- the phases take a range that begins on a segment of the parse, and nothing else --
+    with the last rank taking the remainder; an input of fewer than 1024 bytes per rank cannot be cut at all: ValueError."""
+    if total // world >= HISTORY:
+        a, b = shard_range(total, rank, world)
+    else:
+        per = (total // world) // SEG * SEG
+        if per == 0:
+            raise ValueError("a stream-exact shard begins on a multiple of %d bytes: %d bytes are too few for %d ranks "
+                             "(at least %d)" % (SEG, total, world, SEG * world))
+        a = rank * per
+        b = total if rank == world - 1 else a + per
+    return layout_of(a, b, total)
 
 
 def p1_entries(layouts, tables):
@@ -157,62 +179,66 @@ def p1_token_plan(counts):
     return skip, tail, owns, pieces
 
 
-def encode_p1_virtual(da, ctxs, data, options=None, compat=0):
+def encode_p1_virtual(da, ctxs, data, options=None, compat=0, layouts=None):
     """All ranks in ONE process (one context per virtual rank, any devices): the same phases and the same
     exchanges as the distributed driver, with Python lists as the network.  Used by the GPU tests on a
-    single-GPU box.  Returns the stitched stream (bytes)."""
+    single-GPU box.  layouts: the ranks' layouts (layout_of) where they are not p1_layout's -- any cuts at multiples of
+    1024 bytes.  Returns the stitched stream (bytes)."""
     import torch
     options = options if options is not None else da.Compression.Default
     world = len(ctxs)
     total = len(data)
-    lay = [p1_layout(total, r, world) for r in range(world)]
+    lay = list(layouts) if layouts is not None else [p1_layout(total, r, world) for r in range(world)]
+    assert len(lay) == world
     bufs, shards = [], []
-    for r in range(world):
-        L = lay[r]
-        t = torch.frombuffer(bytearray(data[L["g_lo"]:L["g_hi"]]) + bytearray(16), dtype=torch.uint8).to(
-            "cuda:%d" % ctxs[r].device)
-        bufs.append(t)
-        shards.append(da.Shard(ctxs[r], t.data_ptr(), L["g_hi"] - L["g_lo"], L["lo"], L["hi"], L["g_lo"], total,
-                               options, compat))
-    entries = p1_spec_entries(lay, [s.spec() for s in shards])                 # exchange 0: three numbers per rank
-    if entries is None:
-        tables = [s.exit_table() for s in shards]                              # exchange 1 (periodic data: the exact way)
-        entries = p1_entries(lay, tables)
-    toks = [shards[r].emit(entries[r] - lay[r]["g_lo"]) for r in range(world)]  # (count, dptr)
-    counts = [c for c, _ in toks]                                              # exchange 2
-    skip, tail, owns, pieces = p1_token_plan(counts)
-    costs = []
-    keep = []
-    for r in range(world):                                                     # exchange 3: straddling tokens
-        tail_ptr = 0
-        if len(pieces[r]) == 1:
-            tail_ptr = toks[pieces[r][0][0]][1]
-        elif pieces[r]:  # the block runs over several ranks to the right: their heads, one after the other
-            t = torch.empty(tail[r], dtype=torch.int32, device=bufs[r].device)
-            off = 0
-            for q, k in pieces[r]:
-                ctypes_copy_d2d(t.data_ptr() + 4 * off, toks[q][1], 4 * k)
-                off += k
-            keep.append(t)
-            tail_ptr = t.data_ptr()
-        costs.append(shards[r].blocks(skip[r], tail_ptr, tail[r], owns[r]))
-    allc = [c for cs in costs for c in cs]                                     # exchange 4
-    plans, total_bits = da.plan_blocks(allc, compat)
-    out = torch.zeros((total_bits + 7) // 8 + 16, dtype=torch.uint8)
-    b0 = 0
-    for r in range(world):
-        nb = len(costs[r])
-        mine = plans[b0:b0 + nb]
-        end_bit = plans[b0 + nb][2] if b0 + nb < len(plans) else total_bits
-        b0 += nb
-        if not nb:
-            continue
-        cap = (end_bit - mine[0][2]) // 8 + 64
-        dev = torch.empty(cap, dtype=torch.uint8, device=bufs[r].device)
-        fb, nbytes = shards[r].pack(mine, end_bit, dev.data_ptr(), cap)
-        out[fb:fb + nbytes] |= dev[:nbytes].cpu()                             # exchange 5: OR-stitch
-    for s in shards:
-        s.close()
+    try:  # (whatever happens, the contexts get their shards back: a context that holds one refuses every other encode)
+        for r in range(world):
+            L = lay[r]
+            t = torch.frombuffer(bytearray(data[L["g_lo"]:L["g_hi"]]) + bytearray(16), dtype=torch.uint8).to(
+                "cuda:%d" % ctxs[r].device)
+            bufs.append(t)
+            shards.append(da.Shard(ctxs[r], t.data_ptr(), L["g_hi"] - L["g_lo"], L["lo"], L["hi"], L["g_lo"], total,
+                                   options, compat))
+        entries = p1_spec_entries(lay, [s.spec() for s in shards])                 # exchange 0: three numbers per rank
+        if entries is None:
+            tables = [s.exit_table() for s in shards]                              # exchange 1 (periodic data: the exact way)
+            entries = p1_entries(lay, tables)
+        toks = [shards[r].emit(entries[r] - lay[r]["g_lo"]) for r in range(world)]  # (count, dptr)
+        counts = [c for c, _ in toks]                                              # exchange 2
+        skip, tail, owns, pieces = p1_token_plan(counts)
+        costs = []
+        keep = []
+        for r in range(world):                                                     # exchange 3: straddling tokens
+            tail_ptr = 0
+            if len(pieces[r]) == 1:
+                tail_ptr = toks[pieces[r][0][0]][1]
+            elif pieces[r]:  # the block runs over several ranks to the right: their heads, one after the other
+                t = torch.empty(tail[r], dtype=torch.int32, device=bufs[r].device)
+                off = 0
+                for q, k in pieces[r]:
+                    ctypes_copy_d2d(t.data_ptr() + 4 * off, toks[q][1], 4 * k)
+                    off += k
+                keep.append(t)
+                tail_ptr = t.data_ptr()
+            costs.append(shards[r].blocks(skip[r], tail_ptr, tail[r], owns[r]))
+        allc = [c for cs in costs for c in cs]                                     # exchange 4
+        plans, total_bits = da.plan_blocks(allc, compat)
+        out = torch.zeros((total_bits + 7) // 8 + 16, dtype=torch.uint8)
+        b0 = 0
+        for r in range(world):
+            nb = len(costs[r])
+            mine = plans[b0:b0 + nb]
+            end_bit = plans[b0 + nb][2] if b0 + nb < len(plans) else total_bits
+            b0 += nb
+            if not nb:
+                continue
+            cap = (end_bit - mine[0][2]) // 8 + 64
+            dev = torch.empty(cap, dtype=torch.uint8, device=bufs[r].device)
+            fb, nbytes = shards[r].pack(mine, end_bit, dev.data_ptr(), cap)
+            out[fb:fb + nbytes] |= dev[:nbytes].cpu()                             # exchange 5: OR-stitch
+    finally:
+        for s in shards:
+            s.close()
     return bytes(out[: (total_bits + 7) // 8].numpy())
 
 

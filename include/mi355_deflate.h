@@ -829,6 +829,8 @@ int mi355_shard_blocks_ex(mi355_shard* s, uint64_t skip_tokens, const void* d_ta
                           int owns_final, uint64_t* n_blocks, mi355_block_cost* costs, size_t costs_cap);
 int mi355_plan_blocks(const mi355_block_cost* costs, size_t n, uint32_t compat, mi355_block_info* plans,
                       uint64_t* total_bits);
+/* MI355_E_ARG if a Stored block of the rank ends behind the bytes the rank holds -- or, under MI355_COMPAT_Q13, a Stored block
+ * flagged q13 less than 32768 bytes in front of their end: the reference's bytes for it lie that much further on. */
 int mi355_shard_pack(mi355_shard* s, const mi355_block_info* plans, uint64_t end_bit, void* d_out, size_t out_cap,
                      uint64_t* first_byte, size_t* n_bytes);
 void mi355_shard_end(mi355_shard* s);
