@@ -2223,7 +2223,15 @@ int stream_encode(mi355_deflate_stream* s, bool finish) {
     s->emitted = s->total;
     if (finish) return MI355_OK;
     // let go of what no later segment can see
-    const uint64_t want = (s->emitted >= 3ull * WINDOW_SIZE) ? (s->emitted - WINDOW_SIZE) / WINDOW_SIZE * WINDOW_SIZE : 0;
+    uint64_t want = (s->emitted >= 3ull * WINDOW_SIZE) ? (s->emitted - WINDOW_SIZE) / WINDOW_SIZE * WINDOW_SIZE : 0;
+    // A skew point at want - 1 or at want files position `want` a byte late, under d[want - 1] (stages.h skewed_ab), and `want`
+    // is a candidate of the position 32768 behind it.  A buffer that began at `want` would have neither the point (want - 1) nor
+    // the byte in front of it (the kernels read 0 in front of the buffer): one more window stays
+    // (tests/flush_cases.py trim_skew_at_base_minus_1_F65535_q65536, trim_skew_at_base_own_hash_F65536_q65536).
+    // This is the one way to a base of 32768.  Nothing of the stream's first window can show from there: the re-warm points
+    // are cleared below, and every position still to be encoded lies at 98304 or behind, out of reach of 32768 and 32769.
+    auto skewed = [&](uint64_t f) { return std::find(s->skew.begin(), s->skew.end(), f) != s->skew.end(); };
+    if (want && (skewed(want - 1) || skewed(want))) want -= WINDOW_SIZE;
     if (want > s->base) {
         s->win.erase(s->win.begin(), s->win.begin() + (size_t)(want - s->base));
         s->base = want;
