@@ -274,6 +274,19 @@ struct mi355_deflate_ctx {
     bool mp_ev_ok = false;
     float mp_ms[5] = {};               // mi355_inflate_members_last_parallel_stages: find, walk, decode, windows, resolve
     uint64_t mp_stats[6] = {};         // mi355_inflate_members_last_parallel
+    // deflate_bgzf.inc: the arena the members of a BGZF encode are packed into, the table, offsets and rows behind them (device;
+    // page-locked staging of the one copy back), and the file of a host-buffer call
+    uint8_t* bz_arena = nullptr;
+    size_t bz_arena_cap = 0;
+    uint8_t* bz_tab = nullptr;
+    size_t bz_tab_cap = 0;
+    uint8_t* bz_host = nullptr;
+    size_t bz_host_cap = 0;
+    uint8_t* bz_out = nullptr;
+    size_t bz_out_cap = 0;
+    hipEvent_t bz_ev[4] = {};          // around the packed encode and the two launches, when the stage clocks are on
+    bool bz_ev_ok = false;
+    float bz_ms[3] = {};               // mi355_bgzf_last_stages: packed encode, place, gather
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1799,6 +1812,12 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
         for (int k = 0; k < 2; k++) (void)hipEventDestroy(c->m_ev[k]);
     if (c->mp_ev_ok)
         for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->mp_ev[k]);
+    if (c->bz_arena) (void)hipFree(c->bz_arena);
+    if (c->bz_tab) (void)hipFree(c->bz_tab);
+    if (c->bz_host) (void)hipHostFree(c->bz_host);
+    if (c->bz_out) (void)hipFree(c->bz_out);
+    if (c->bz_ev_ok)
+        for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->bz_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

@@ -3597,6 +3597,7 @@ __global__ void k_gzip_frame(DevScalars* sc, uint8_t* out, const uint8_t* hdr, u
 #include "deflate_multi.inc"
 #include "deflate_batch.inc"
 #include "decode_host.inc"
+#include "deflate_bgzf.inc"
 #include "deflate_verify.inc"
 #include "deflate_inflate.inc"
 #include "deflate_table_inflate.inc"

@@ -9,6 +9,7 @@ or a gfx950 device is missing.
 import ctypes as C
 import enum
 import os
+import struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355_DEFLATE_LIB", os.path.join(_HERE, "libmi355deflate.so"))
@@ -369,6 +370,13 @@ def load():
     L.mi355_inflate_seek_last_read_cuts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mi355_inflate_seek_last_read_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.mi355_deflate_ctx_config_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+    L.mi355_bgzf_bound.argtypes = [C.c_size_t, C.c_size_t]
+    L.mi355_bgzf_bound.restype = C.c_size_t
+    L.mi355_bgzf_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Opts), C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    L.mi355_bgzf_encode.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(Opts), C.c_size_t, C.c_void_p, C.c_size_t,
+                                    C.POINTER(C.c_size_t), C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_bgzf_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -405,6 +413,7 @@ EXPORTED = [
     "mi355_inflate_seek_points", "mi355_inflate_seek_read", "mi355_inflate_seek_read_device", "mi355_inflate_seek_read_batch_device",
     "mi355_inflate_seek_last_read", "mi355_inflate_seek_cuts", "mi355_inflate_seek_cut_info", "mi355_inflate_seek_last_read_cuts",
     "mi355_inflate_seek_last_read_stages", "mi355_deflate_ctx_config_get",
+    "mi355_bgzf_bound", "mi355_bgzf_encode", "mi355_bgzf_encode_device", "mi355_bgzf_last_stages",
 ]
 
 
@@ -1146,6 +1155,56 @@ class Context:
             self._err(rc)
         return rc, n, rep, members
 
+    # ---- BGZF encode: one input, one blocked gzip file (mi355_bgzf_*) ----
+    def encode_bgzf_raw(self, data, options=Compression.Default, block_size=0, compat=0, out_cap=None, room=None):
+        """mi355_bgzf_encode on host bytes, nothing raised: (rc, out_len, n_members, member dicts, the buffer's bytes).  out_cap None:
+        the bound; 0 hands over no buffer (the size query).  room: entries of the member table handed over (None: all)."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(2, compat, 0)
+        data = bytes(data)
+        if out_cap is None:
+            out_cap = L.mi355_bgzf_bound(len(data), block_size)
+        if room is None:
+            room = len(data) // (block_size or BGZF_BLOCK_MAX) + 2
+        out = (C.c_uint8 * out_cap)() if out_cap else None
+        arr = (MemberInfo * max(room, 1))()
+        n, nm = C.c_size_t(0), C.c_size_t(0)
+        rc = L.mi355_bgzf_encode(self._h, data, len(data), C.byref(o), block_size, C.cast(out, C.c_void_p) if out_cap else None, out_cap,
+                                 C.byref(n), arr if room else None, room, C.byref(nm))
+        return rc, n.value, nm.value, [arr[k].as_dict() for k in range(min(nm.value, room))], bytes(out) if out_cap else b""
+
+    def encode_bgzf(self, data, options=Compression.Default, block_size=0, compat=0):
+        """Host bytes -> (the BGZF file, its members): the input in slices of block_size bytes (0: 65280), a gzip member that states
+        its size per slice, the end-of-file marker last (mi355_bgzf_encode).  members: dicts of mi355_member_info in file order."""
+        rc, n, _nm, members, buf = self.encode_bgzf_raw(data, options, block_size, compat)
+        if rc != OK:
+            self._err(rc)
+        return buf[:n], members
+
+    def encode_bgzf_device(self, d_in_ptr, in_len, d_out_ptr, out_cap, options=Compression.Default, block_size=0, compat=0, stream=0,
+                           room=None, check=True):
+        """mi355_bgzf_encode_device on device pointers (d_out 16-byte aligned): (rc, out_len, n_members, member dicts); rc is OK or
+        E_OUT_TOO_SMALL with check=False, else anything but OK raises."""
+        L = load()
+        o = CompressionOptions.from_(options).to_c(2, compat, 0)
+        if room is None:
+            room = in_len // (block_size or BGZF_BLOCK_MAX) + 2
+        arr = (MemberInfo * max(room, 1))()
+        n, nm = C.c_size_t(0), C.c_size_t(0)
+        rc = L.mi355_bgzf_encode_device(self._h, C.c_void_p(d_in_ptr), in_len, C.byref(o), block_size, C.c_void_p(d_out_ptr), out_cap,
+                                        C.byref(n), arr if room else None, room, C.byref(nm), C.c_void_p(stream))
+        if rc != OK and (check or rc != E_OUT_TOO_SMALL):
+            self._err(rc)
+        return rc, n.value, nm.value, [arr[k].as_dict() for k in range(min(nm.value, room))]
+
+    def bgzf_stages(self):
+        """mi355_bgzf_last_stages: HIP-event ms of the last BGZF encode per stage (zeros without CFG_STAGE_CLOCKS)"""
+        ms = (C.c_float * 3)()
+        rc = load().mi355_bgzf_last_stages(self._h, ms)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("packed_encode_ms", "place_ms", "gather_ms"), ms))
+
     def inflate_members_stages(self):
         """mi355_inflate_members_last_stages: HIP-event ms of the last members call per launch kind (zeros without CFG_STAGE_CLOCKS)"""
         ms = (C.c_float * 6)()
@@ -1374,6 +1433,29 @@ def deflate_bytes_batch_packed(datas, ctx=None):
 
 
 # ---- the reference's Write encoders (src/writer.rs) ---------------------------------------------
+BGZF_BLOCK_MAX = 65280  # bgzip's 0xff00: the largest (and the default) block_size of a BGZF encode
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_bound(n, block_size=0):
+    """mi355_bgzf_bound: the output room that always suffices for a BGZF encode of n bytes (no GPU needed; 0 for a bad block_size)"""
+    return load().mi355_bgzf_bound(n, block_size)
+
+
+def bgzf_bytes(data, options=Compression.Default, block_size=0, ctx=None):
+    """The BGZF file of `data` (Context.encode_bgzf without the member table)"""
+    return (ctx or default_context()).encode_bgzf(data, options, block_size)[0]
+
+
+def bgzf_gzi(members):
+    """The .gzi index of `bgzip -i` for a member table (dicts or MemberInfo, the end-of-file marker included or not): a little-endian
+    u64 count, then (compressed offset, uncompressed offset) u64 pairs for every data member but the first."""
+    get = (lambda m, k: m[k]) if members and isinstance(members[0], dict) else getattr
+    data = [m for m in members if get(m, "out_len")]
+    pairs = [(get(m, "in_off"), get(m, "out_off")) for m in data[1:]]
+    return struct.pack("<Q", len(pairs)) + b"".join(struct.pack("<QQ", a, b) for a, b in pairs)
+
+
 class _Encoder:
     _wrapper = 0
 

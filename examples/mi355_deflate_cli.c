@@ -1,12 +1,17 @@
 /* A plain C program over the C ABI of include/mi355_deflate.h (what the Rust shim of INTEGRATION.md
  * binds): compresses a file on the GPU, or with -d decompresses one.
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
+ *   mi355_deflate_cli --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT
  *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
  *   mi355_deflate_cli -d --members [-gzip] IN OUT
  *   mi355_deflate_cli -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
  * mi355_deflate_verify: what `gzip -t` answers), prints the report and exits with status 3 if it does not inflate to the input.
+ * --bgzf writes a BGZF file (mi355_bgzf_encode: what bgzip writes and htslib, `gzip -d` and -d --members read): IN in slices of N bytes
+ * (--block N: 1 to 65280, the default), a gzip member that states its size per slice, the end-of-file marker last.  Not together with a
+ * format switch, -chunk or -d.  With --verify the file is inflated again on the GPU (mi355_inflate_members) and compared with IN
+ * before it is written; exit status 3 if it differs.
  * -d / --decompress inflates IN (a raw, zlib or gzip stream by the format switch) to OUT on the GPU: mi355_inflate once without a
  * buffer for the size, once more for the bytes; exits with status 3 and the report if the stream is not valid.  With --parallel the
  * two calls are mi355_inflate_parallel: the block table of the stream is found on the GPU and every entry decoded by a wave of its own
@@ -35,7 +40,8 @@ int main(int argc, char** argv) {
     size_t chunk = 0;
     int verify = 0, decompress = 0, parallel = 0, members = 0, format_given = 0, ranged = 0;
     unsigned long long r_off = 0, r_len = 0, cut = 0;
-    int cut_given = 0;
+    int cut_given = 0, bgzf = 0, block_given = 0;
+    unsigned long long block = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "-raw")) wrapper = 0, format_given = 1;
@@ -61,14 +67,20 @@ int main(int argc, char** argv) {
             char* end = NULL;
             cut = strtoull(argv[++a], &end, 10);
             cut_given = end && end != argv[a] && !*end ? 1 : -1;
+        } else if (!strcmp(argv[a], "--bgzf") || !strcmp(argv[a], "-bgzf")) bgzf = 1;
+        else if ((!strcmp(argv[a], "--block") || !strcmp(argv[a], "-block")) && a + 1 < argc) {
+            char* end = NULL;
+            block = strtoull(argv[++a], &end, 10);
+            block_given = end && end != argv[a] && !*end && block >= 1 && block <= 65280 ? 1 : -1;
         } else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
     /* --members is gzip by definition: another format switch beside it is refused, not ignored */
     if (argc - a != 2 || ((parallel || members || ranged) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2) ||
-        ranged < 0 || (ranged && (parallel || members)) || cut_given < 0 || (cut_given && !ranged)) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
-                argv[0], argv[0], argv[0], argv[0]);
+        ranged < 0 || (ranged && (parallel || members)) || cut_given < 0 || (cut_given && !ranged) || block_given < 0 || (block_given && !bgzf) ||
+        (bgzf && (decompress || format_given || chunk))) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     FILE* f = fopen(argv[a], "rb");
@@ -180,6 +192,38 @@ int main(int argc, char** argv) {
     mi355_deflate_preset(level, &o); /* Compression::{Fast,Default,Best} */
     o.wrapper = (uint8_t)wrapper;
 
+    if (bgzf) { /* one blocked gzip file; --verify: inflated again member by member and compared with the input */
+        size_t cap = mi355_bgzf_bound(n, (size_t)block), file_len = 0, n_members = 0;
+        uint8_t* file = (uint8_t*)malloc(cap);
+        if (!file) return fail("malloc", -1, NULL);
+        rc = mi355_bgzf_encode(ctx, in, n, &o, (size_t)block, file, cap, &file_len, NULL, 0, &n_members);
+        if (rc) return fail("mi355_bgzf_encode", rc, ctx);
+        mi355_deflate_info binfo;
+        mi355_deflate_last_info(ctx, &binfo);
+        if (verify) {
+            mi355_inflate_report r;
+            size_t got = 0, walked = 0;
+            uint8_t* back = (uint8_t*)malloc(n ? n : 1);
+            if (!back) return fail("malloc", -1, NULL);
+            rc = mi355_inflate_members(ctx, file, file_len, back, n, &got, NULL, 0, &walked, &r);
+            if (rc != MI355_OK && rc != MI355_E_DATA && rc != MI355_E_OUT_TOO_SMALL) return fail("mi355_inflate_members", rc, ctx);
+            const int same = rc == MI355_OK && got == n && walked == n_members && !memcmp(back, in, n);
+            fprintf(stderr, "verify: %s; %lu members, status %u, %llu blocks (%u stored, %u fixed, %u dynamic), %.3f ms\n",
+                    same ? "the file inflates to the input" : "the file does NOT inflate to the input", (unsigned long)walked, r.status,
+                    (unsigned long long)r.n_blocks, r.n_stored, r.n_fixed, r.n_dynamic, r.ms);
+            free(back);
+            if (!same) return 3;
+        }
+        f = fopen(argv[a + 1], "wb");
+        if (!f || fwrite(file, 1, file_len, f) != file_len) return fail("write output", -1, NULL);
+        fclose(f);
+        fprintf(stderr, "%lu -> %lu bytes, %lu members (the end-of-file marker among them), %u blocks\n", (unsigned long)n, (unsigned long)file_len,
+                (unsigned long)n_members, binfo.n_blocks);
+        free(file);
+        free(in);
+        mi355_deflate_ctx_destroy(ctx);
+        return 0;
+    }
     const uint8_t* out = NULL;
     uint8_t* owned = NULL;
     size_t out_len = 0;

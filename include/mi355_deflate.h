@@ -683,6 +683,48 @@ typedef struct {
 } mi355_member_walk; /* 40 bytes */
 int mi355_inflate_members_last_walks(mi355_deflate_ctx* ctx, uint64_t* cand, mi355_member_walk* walks, size_t cap, size_t* n_spans);
 
+/* ---- BGZF encode: one input, one blocked gzip file (the write side of the members calls above) ---------------
+ * The file bgzip writes and htslib, `gzip -d` and mi355_inflate_members read: the input cut into slices of block_size bytes, every
+ * slice a gzip member that states its own size, the members back to back without a byte between them, the 28-byte end-of-file
+ * marker last.  With H = 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 00 00 (FEXTRA, MTIME 0, XFL 0, OS 255, XLEN 6, subfield
+ * 'B','C' of length 2):
+ *     member k = mi355_deflate_encode_gzip(in[k * B, min((k + 1) * B, in_len)), opts, hdr = H)     deflate_bytes_gzip_conf, src/lib.rs:242-267
+ *     with bytes 16..17 replaced by the little-endian 16-bit value len(member k) - 1 (BSIZE)
+ *     marker   = 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00   (the same call on the empty input)
+ * block_size B: 1 to 65280; 0 means 65280 (bgzip's 0xff00).  in_len == 0 gives the marker alone.  A member of at most 65280 input
+ *   bytes is at most 65321 bytes long, which BSIZE can express; the device still checks, and a member longer than 65536 bytes makes
+ *   the call return MI355_E_UNSUPPORTED with no valid file promised.
+ * opts: every level, MI355_FLUSH_FINISH only; opts->wrapper is taken as 2 whatever it holds, as the _gzip entries do.  The other
+ *   checks are the packed batch's: lazy_if_less_than < 3 with Lazy is MI355_E_UNSUPPORTED, a live shard is MI355_E_STATE.
+ *   MI355_E_ARG is decided before the device is touched: a NULL ctx (these calls take no default context), opts or out_len,
+ *   block_size > 65280, a NULL input with in_len > 0, a NULL buffer with out_cap > 0 or a NULL table with members_cap > 0, and
+ *   (_device) a d_out that is not 16-byte aligned.
+ * Capacity: *out_len is always the exact size of the file.  out_cap >= mi355_bgzf_bound(in_len, block_size) always succeeds -- the
+ *   sum of the members' mi355_deflate_bound_ex(len_k, 2, 18, 0) plus 28, computed without a GPU; 0 for a bad block_size -- and so does
+ *   a smaller one that still holds the file.  One that does not: MI355_E_OUT_TOO_SMALL, out[0, out_cap) unspecified, and nothing at
+ *   or beyond out_cap is ever stored.  out == NULL with out_cap == 0 is the size query: it runs the encode and answers
+ *   MI355_E_OUT_TOO_SMALL with the size (a file is never empty: the marker alone is 28 bytes).
+ * members (HOST memory, may be NULL with members_cap 0): mi355_member_info, one entry per member in file order, the marker last with
+ *   out_len 0; flags MI355_MEMBER_HINTED and status 0 in every entry: after a successful call the table mi355_inflate_members
+ *   returns for the file.  Cut at members_cap without an error; *n_members (may be NULL) is the full count.
+ * A member on which the reference panics under MI355_COMPAT_Q13 fails the whole call with MI355_E_REF_PANIC (*out_len 0).
+ * How: the slices are the items of the packed batch above (wrapper 2, the one header H, align 4) in an arena the context owns; one
+ *   workgroup then scans the members' exact lengths in slice order into file offsets, and one launch moves every member from its
+ *   aligned region to its byte offset, writes BSIZE on the way and appends the marker.  Routing of the slices (the batched kernels
+ *   or the one-input path, MI355_CFG_BATCH_BYTES) is the packed batch's and is not visible in the result;
+ *   mi355_deflate_last_info, _last_batch_info and _last_blocks read as after that packed batch.
+ * _device: d_in / d_out are device pointers, hip_stream NULL = the context's stream; the call returns after the stream has drained.
+ * mi355_bgzf_encode: host pointers, staged with plain copies. */
+size_t mi355_bgzf_bound(size_t in_len, size_t block_size);
+int mi355_bgzf_encode_device(mi355_deflate_ctx* ctx, const void* d_in, size_t in_len, const mi355_deflate_opts* opts, size_t block_size,
+                             void* d_out, size_t out_cap, size_t* out_len, mi355_member_info* members, size_t members_cap,
+                             size_t* n_members, void* hip_stream);
+int mi355_bgzf_encode(mi355_deflate_ctx* ctx, const uint8_t* in, size_t in_len, const mi355_deflate_opts* opts, size_t block_size,
+                      uint8_t* out, size_t out_cap, size_t* out_len, mi355_member_info* members, size_t members_cap, size_t* n_members);
+/* A measuring aid like mi355_inflate_members_last_stages: HIP-event milliseconds of the context's last BGZF encode -- the packed
+ * encode, the place, the gather; zeros unless the stage clocks were on (MI355_CFG_STAGE_CLOCKS). */
+int mi355_bgzf_last_stages(mi355_deflate_ctx* ctx, float ms[3]);
+
 /* ---- seek points: any byte range of ONE large stream, decoded from the nearest restart point ---------------
  * mi355_inflate_parallel gives back a whole stream; these calls give back PART of one without an output buffer for the rest and
  * without decoding the rest.  A handle keeps the stream's table (the caller's, or the one mi355_inflate_index finds) and, for some
