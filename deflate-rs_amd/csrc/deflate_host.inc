@@ -287,6 +287,11 @@ struct mi355_deflate_ctx {
     hipEvent_t bz_ev[4] = {};          // around the packed encode and the two launches, when the stage clocks are on
     bool bz_ev_ok = false;
     float bz_ms[3] = {};               // mi355_bgzf_last_stages: packed encode, place, gather
+    // deflate_bgzf_read.inc: BGZF reads (their scratch slots live in t_dev, their descriptors in v_dev)
+    hipEvent_t br_ev[5] = {};          // around the launches of a read's set, when the stage clocks are on
+    bool br_ev_ok = false;
+    float br_ms[3] = {};               // mi355_bgzf_last_read_stages: decode and clip, checksums, trailers
+    uint64_t br_stats[6] = {};         // mi355_bgzf_last_read
 };
 void shard_destroy(struct mi355_shard* s);
 // deflate_long.inc: inputs of any length and never-flushed streams, walked in ranges
@@ -1818,6 +1823,8 @@ void mi355_deflate_ctx_destroy(mi355_deflate_ctx* c) {
     if (c->bz_out) (void)hipFree(c->bz_out);
     if (c->bz_ev_ok)
         for (int k = 0; k < 4; k++) (void)hipEventDestroy(c->bz_ev[k]);
+    if (c->br_ev_ok)
+        for (int k = 0; k < 5; k++) (void)hipEventDestroy(c->br_ev[k]);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;

@@ -3605,3 +3605,4 @@ __global__ void k_gzip_frame(DevScalars* sc, uint8_t* out, const uint8_t* hdr, u
 #include "deflate_bigmembers_inflate.inc"
 #include "deflate_members_inflate.inc"
 #include "deflate_seek_inflate.inc"
+#include "deflate_bgzf_read.inc"

@@ -211,6 +211,12 @@ class SeekRange(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class BgzfInfo(C.Structure):
+    """mi355_bgzf_info (40 bytes)"""
+    _fields_ = [("total", C.c_uint64), ("n_members", C.c_uint64), ("file_len", C.c_uint64), ("host_bytes", C.c_uint64),
+                ("max_out_len", C.c_uint64)]
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -377,6 +383,23 @@ def load():
     L.mi355_bgzf_encode.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(Opts), C.c_size_t, C.c_void_p, C.c_size_t,
                                     C.POINTER(C.c_size_t), C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t)]
     L.mi355_bgzf_last_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_bgzf_index_build_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_bgzf_index_build.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(InflateReport)]
+    L.mi355_bgzf_index_from_members.argtypes = [C.POINTER(MemberInfo), C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mi355_bgzf_index_free.argtypes = [C.c_void_p]
+    L.mi355_bgzf_index_free.restype = None
+    L.mi355_bgzf_index_info.argtypes = [C.c_void_p, C.POINTER(BgzfInfo)]
+    L.mi355_bgzf_index_members.argtypes = [C.c_void_p, C.POINTER(MemberInfo), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.mi355_bgzf_voffset.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mi355_bgzf_uoffset.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mi355_bgzf_read_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                         C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_bgzf_read.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+                                  C.POINTER(InflateReport)]
+    L.mi355_bgzf_read_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SeekRange), C.c_size_t, C.POINTER(InflateReport),
+                                               C.c_void_p]
+    L.mi355_bgzf_last_read.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mi355_bgzf_last_read_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -414,6 +437,9 @@ EXPORTED = [
     "mi355_inflate_seek_last_read", "mi355_inflate_seek_cuts", "mi355_inflate_seek_cut_info", "mi355_inflate_seek_last_read_cuts",
     "mi355_inflate_seek_last_read_stages", "mi355_deflate_ctx_config_get",
     "mi355_bgzf_bound", "mi355_bgzf_encode", "mi355_bgzf_encode_device", "mi355_bgzf_last_stages",
+    "mi355_bgzf_index_build", "mi355_bgzf_index_build_device", "mi355_bgzf_index_from_members", "mi355_bgzf_index_free",
+    "mi355_bgzf_index_info", "mi355_bgzf_index_members", "mi355_bgzf_voffset", "mi355_bgzf_uoffset",
+    "mi355_bgzf_read", "mi355_bgzf_read_device", "mi355_bgzf_read_batch_device", "mi355_bgzf_last_read", "mi355_bgzf_last_read_stages",
 ]
 
 
@@ -549,6 +575,169 @@ class SeekIndex:
             out.append(host[at:at + got])
             at += length
         return out
+
+
+class BgzfIndex:
+    """The member table of a BGZF file (mi355_bgzf_index), for reads of byte ranges of its uncompressed data.  It holds host memory
+    only and is bound to no context.  Made by Context.bgzf_index / Context.bgzf_index_device, which keep the context and the file for
+    the reads, or by bgzf_index_from_members, whose reads take ctx= and file= (or d_file_ptr=)."""
+
+    def __init__(self, handle, report=None, ctx=None, file=None, d_file_ptr=0):
+        self._h, self.report, self._ctx, self._file, self._d_file = handle, report, ctx, file, d_file_ptr
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().mi355_bgzf_index_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def _check(rc, what):
+        if rc != OK:
+            raise DeflateError(rc, "bgzf index: " + what)
+
+    def info(self):
+        """mi355_bgzf_index_info"""
+        i = BgzfInfo()
+        self._check(load().mi355_bgzf_index_info(self._h, C.byref(i)), "bad handle")
+        return {k: getattr(i, k) for k, _ in BgzfInfo._fields_}
+
+    def members(self):
+        """mi355_bgzf_index_members: the table, one dict per member"""
+        n = C.c_size_t(0)
+        load().mi355_bgzf_index_members(self._h, None, 0, C.byref(n))
+        arr = (MemberInfo * max(n.value, 1))()
+        self._check(load().mi355_bgzf_index_members(self._h, arr, n.value, C.byref(n)), "bad handle")
+        return [arr[k].as_dict() for k in range(n.value)]
+
+    def voffset(self, uoff):
+        """mi355_bgzf_voffset: htslib's virtual offset of an uncompressed offset"""
+        v = C.c_uint64(0)
+        self._check(load().mi355_bgzf_voffset(self._h, uoff, C.byref(v)), "no virtual offset for %d" % uoff)
+        return v.value
+
+    def uoffset(self, voff):
+        """mi355_bgzf_uoffset: the uncompressed offset of a virtual offset"""
+        u = C.c_uint64(0)
+        self._check(load().mi355_bgzf_uoffset(self._h, voff, C.byref(u)), "no such virtual offset: %#x" % voff)
+        return u.value
+
+    def _context(self, ctx):
+        ctx = ctx or self._ctx
+        if ctx is None:
+            raise ValueError("this index was made from a member table: pass ctx=")
+        return ctx
+
+    def last_read(self, ctx=None):
+        """mi355_bgzf_last_read of the context the reads ran on"""
+        ctx = self._context(ctx)
+        v = (C.c_uint64 * 6)()
+        rc = load().mi355_bgzf_last_read(ctx._h, v)
+        if rc != OK:
+            ctx._err(rc)
+        return dict(zip(("distinct", "in_place", "scratch", "pieces", "sets", "copied"), v))
+
+    def read_raw(self, off, length, ctx=None, file=None):
+        """mi355_bgzf_read on host bytes: (rc, got, report dict, the bytes that hold data); rc is OK or E_DATA"""
+        ctx = self._context(ctx)
+        file = self._file if file is None else bytes(file)
+        if file is None:
+            raise ValueError("this index keeps no file: pass file=")
+        room = min(length, self.info()["total"])
+        out = C.create_string_buffer(max(room, 1))
+        got, r = C.c_uint64(0), InflateReport()
+        rc = load().mi355_bgzf_read(ctx._h, self._h, file, off, min(length, room), C.cast(out, C.c_void_p) if room else None, C.byref(got),
+                                    C.byref(r))
+        if rc not in (OK, E_DATA):
+            ctx._err(rc)
+        return rc, got.value, r.as_dict(), out.raw[:got.value]
+
+    def read(self, off, length, ctx=None, file=None):
+        """pread over the uncompressed bytes: [off, off + length), fewer at the end; DeflateError(E_DATA, ...) if a touched member
+        is not what the index claims"""
+        ctx = self._context(ctx)
+        rc, _got, _rep, data = self.read_raw(off, length, ctx, file)
+        if rc != OK:
+            ctx._err(rc)
+        return data
+
+    def read_device(self, off, length, d_out_ptr, d_file_ptr=0, ctx=None, stream=0, check=False):
+        """mi355_bgzf_read_device: (rc, got, report dict).  d_file_ptr 0: the pointer Context.bgzf_index_device was given."""
+        ctx = self._context(ctx)
+        got, r = C.c_uint64(0), InflateReport()
+        rc = load().mi355_bgzf_read_device(ctx._h, self._h, C.c_void_p(d_file_ptr or self._d_file), off, length, C.c_void_p(d_out_ptr),
+                                           C.byref(got), C.byref(r), C.c_void_p(stream))
+        if rc not in (OK, E_DATA) or (check and rc != OK):
+            ctx._err(rc)
+        return rc, got.value, r.as_dict()
+
+    def read_batch_device(self, ranges, d_file_ptr=0, ctx=None, stream=0, check=False):
+        """mi355_bgzf_read_batch_device: ranges = [(off, len, d_out_ptr)]; every touched member is decoded once.  Returns (rc,
+        [(status, got, report dict)])."""
+        ctx = self._context(ctx)
+        n = len(ranges)
+        arr = (SeekRange * max(n, 1))()
+        for k, (off, length, ptr) in enumerate(ranges):
+            arr[k].off, arr[k].len, arr[k].out = off, length, ptr
+        reps = (InflateReport * max(n, 1))()
+        rc = load().mi355_bgzf_read_batch_device(ctx._h, self._h, C.c_void_p(d_file_ptr or self._d_file), arr, n, reps, C.c_void_p(stream))
+        if rc not in (OK, E_DATA, E_UNSUPPORTED) or (check and rc != OK):
+            ctx._err(rc)
+        return rc, [(arr[k].status, arr[k].got, reps[k].as_dict()) for k in range(n)]
+
+    def read_batch(self, ranges, ctx=None, file=None):
+        """[(off, len), ...] -> [bytes, ...] from host bytes: the file goes to the device once, the ranges through one call"""
+        import torch
+
+        ctx = self._context(ctx)
+        file = self._file if file is None else bytes(file)
+        if file is None:
+            raise ValueError("this index keeps no file: pass file=")
+        dev = "cuda:%d" % ctx.device
+        d_file = torch.frombuffer(bytearray(file) or bytearray(1), dtype=torch.uint8).to(dev)
+        total = self.info()["total"]
+        rooms = [min(length, max(total - off, 0)) for off, length in ranges]
+        buf = torch.empty(max(sum(rooms), 1), dtype=torch.uint8, device=dev)
+        at, items = 0, []
+        for (off, _length), room in zip(ranges, rooms):
+            items.append((off, room, buf.data_ptr() + at if room else 0))
+            at += room
+        _rc, res = self.read_batch_device(items, d_file.data_ptr(), ctx, check=True)
+        host = buf.cpu().numpy().tobytes()
+        out, at = [], 0
+        for room, (_st, got, _rep) in zip(rooms, res):
+            out.append(host[at:at + got])
+            at += room
+        return out
+
+
+def bgzf_index_from_members(members, file_len):
+    """mi355_bgzf_index_from_members: a BgzfIndex from the table mi355_bgzf_encode or a successful mi355_inflate_members returned
+    ([MemberInfo], or dicts as MemberInfo.as_dict gives them).  No GPU and no context."""
+    arr = (MemberInfo * max(len(members), 1))()
+    for k, m in enumerate(members):
+        if isinstance(m, dict):
+            st = m.get("status", 0)
+            st = VERIFY_STATUS.index(st) if isinstance(st, str) else st
+            arr[k] = MemberInfo(m["in_off"], m["in_len"], m["out_off"], m["out_len"], m.get("flags", 0), st)
+        else:
+            arr[k] = MemberInfo(m.in_off, m.in_len, m.out_off, m.out_len, m.flags, m.status)
+    h = C.c_void_p()
+    rc = load().mi355_bgzf_index_from_members(arr if len(members) else None, len(members), file_len, C.byref(h))
+    if rc != OK:
+        raise DeflateError(rc, "bgzf index: the member table does not describe a file of %d bytes" % file_len)
+    return BgzfIndex(h)
 
 
 class Context:
@@ -911,6 +1100,33 @@ class Context:
         arr, nb = self._block_table(blocks)
         return self._seek(lambda h, r: load().mi355_inflate_seek_build_device(self._h, C.c_void_p(d_stream_ptr), stream_len, wrapper, arr, nb,
                                                                              spacing, h, r, C.c_void_p(stream)), cut)
+
+    # ---- BGZF reads: byte ranges of a blocked gzip file from its member index (mi355_bgzf_index_*, mi355_bgzf_read*) ----
+    def bgzf_index(self, file):
+        """mi355_bgzf_index_build on host bytes -> BgzfIndex, which keeps this context and the file for its reads.  A file that is
+        not BGZF members from its first to its last byte raises DeflateError(E_DATA, ...)."""
+        file = bytes(file)
+        h, r = C.c_void_p(), InflateReport()
+        rc = load().mi355_bgzf_index_build(self._h, file, len(file), C.byref(h), C.byref(r))
+        if rc != OK:
+            self._err(rc)
+        return BgzfIndex(h, r.as_dict(), self, file)
+
+    def bgzf_index_device(self, d_file_ptr, file_len, stream=0):
+        """mi355_bgzf_index_build_device: the same for a file in device memory, whose pointer the index remembers for read_device"""
+        h, r = C.c_void_p(), InflateReport()
+        rc = load().mi355_bgzf_index_build_device(self._h, C.c_void_p(d_file_ptr), file_len, C.byref(h), C.byref(r), C.c_void_p(stream))
+        if rc != OK:
+            self._err(rc)
+        return BgzfIndex(h, r.as_dict(), self, None, d_file_ptr)
+
+    def bgzf_last_read_stages(self):
+        """mi355_bgzf_last_read_stages: ms per launch kind of the last BGZF read (zeros unless CFG_STAGE_CLOCKS was on)"""
+        v = (C.c_float * 3)()
+        rc = load().mi355_bgzf_last_read_stages(self._h, v)
+        if rc != OK:
+            self._err(rc)
+        return dict(zip(("decode", "checksums", "trailers"), v))
 
     # ---- verify: does the stream inflate to the input? (mi355_deflate_verify*) ----
     @staticmethod

@@ -4,6 +4,7 @@
  *   mi355_deflate_cli --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT
  *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
  *   mi355_deflate_cli -d --members [-gzip] IN OUT
+ *   mi355_deflate_cli -d --members --range OFF:LEN [-gzip] IN OUT
  *   mi355_deflate_cli -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT
  * -chunk N drives the streaming handle (write N bytes at a time) instead of the one-shot call.
  * --verify checks the stream against the input on the GPU before it is written (mi355_deflate_last_blocks +
@@ -19,7 +20,9 @@
  * BGZF, `cat a.gz b.gz` -- and the two calls are mi355_inflate_members (plain -d -gzip takes exactly one member); --members with -raw or -zlib is refused with the usage text.
  * With --range OFF:LEN only the bytes [OFF, OFF + LEN) of what IN inflates to are written (fewer at its end, like pread): a seek index
  * is built (mi355_inflate_seek_build: the table found on the GPU, a window kept every MiB of output) and the range is decoded from the
- * nearest point (mi355_inflate_seek_read); not together with --parallel or --members.  With --cut BYTES the index also remembers
+ * nearest point (mi355_inflate_seek_read); not together with --parallel.  With --members --range IN is a BGZF file: its member index
+ * is built from the file's own size fields without decoding anything (mi355_bgzf_index_build) and only the members that hold the
+ * range are decoded and verified (mi355_bgzf_read); --cut does not go with it.  With --cut BYTES the index also remembers
  * a cut every BYTES of output inside its table entries (MI355_CFG_INFLATE_SEEK_CUT_BYTES: 64 bytes to 1 GiB) and the read decodes a
  * wave per cut; only together with --range.
  * Build:  gcc -O2 -Iinclude examples/mi355_deflate_cli.c -Ldeflate-rs_amd -lmi355deflate \
@@ -77,10 +80,10 @@ int main(int argc, char** argv) {
     }
     /* --members is gzip by definition: another format switch beside it is refused, not ignored */
     if (argc - a != 2 || ((parallel || members || ranged) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2) ||
-        ranged < 0 || (ranged && (parallel || members)) || cut_given < 0 || (cut_given && !ranged) || block_given < 0 || (block_given && !bgzf) ||
+        ranged < 0 || (ranged && parallel) || cut_given < 0 || (cut_given && (!ranged || members)) || block_given < 0 || (block_given && !bgzf) ||
         (bgzf && (decompress || format_given || chunk))) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
-                argv[0], argv[0], argv[0], argv[0], argv[0]);
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --members --range OFF:LEN [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
+                argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     FILE* f = fopen(argv[a], "rb");
@@ -95,6 +98,41 @@ int main(int argc, char** argv) {
     mi355_deflate_ctx* ctx = NULL;
     int rc = mi355_deflate_ctx_create(0, &ctx);
     if (rc) return fail("mi355_deflate_ctx_create (no GPU? there is no CPU fallback)", rc, NULL);
+    if (decompress && members && ranged) { /* a BGZF file: its member index from its own claims, then the members that hold the range */
+        mi355_inflate_report r;
+        mi355_bgzf_index* idx = NULL;
+        mi355_bgzf_info info;
+        uint64_t got = 0, v[6];
+        rc = mi355_bgzf_index_build(ctx, in, n, &idx, &r);
+        if (rc == MI355_E_DATA) {
+            fprintf(stderr, "index: no BGZF member behind output byte %llu\n%s\n", (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
+            return 3;
+        }
+        if (rc) return fail("mi355_bgzf_index_build", rc, ctx);
+        mi355_bgzf_index_info(idx, &info);
+        const uint64_t room = r_off >= info.total ? 0 : (r_len < info.total - r_off ? r_len : info.total - r_off);
+        uint8_t* data = (uint8_t*)malloc(room ? (size_t)room : 1);
+        if (!data) return fail("malloc", -1, NULL);
+        rc = mi355_bgzf_read(ctx, idx, in, r_off, room, data, &got, &r);
+        if (rc == MI355_E_DATA) {
+            fprintf(stderr, "read: status %u at bit %llu, output byte %llu\n%s\n", r.status, (unsigned long long)r.bit,
+                    (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
+            return 3;
+        }
+        if (rc) return fail("mi355_bgzf_read", rc, ctx);
+        mi355_bgzf_last_read(ctx, v);
+        f = fopen(argv[a + 1], "wb");
+        if (!f || fwrite(data, 1, (size_t)got, f) != got) return fail("write output", -1, NULL);
+        fclose(f);
+        fprintf(stderr, "%llu bytes at %llu of %llu; %llu members of %llu decoded, %llu of %lu compressed bytes copied, %llu blocks, %.3f ms\n",
+                (unsigned long long)got, r_off, (unsigned long long)info.total, (unsigned long long)v[0], (unsigned long long)info.n_members,
+                (unsigned long long)v[5], (unsigned long)n, (unsigned long long)r.n_blocks, r.ms);
+        free(data);
+        free(in);
+        mi355_bgzf_index_free(idx);
+        mi355_deflate_ctx_destroy(ctx);
+        return 0;
+    }
     if (decompress && members) { /* a gzip file of any number of members: the size first, then the bytes */
         mi355_inflate_report r;
         size_t need = 0, got = 0, n_members = 0;

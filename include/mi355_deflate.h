@@ -823,6 +823,82 @@ int mi355_inflate_seek_last_read_cuts(mi355_inflate_seek* seek, uint64_t v[4]);
  * cuts), flatten (0 without cuts), windows, resolve; zeros unless the stage clocks were on for the call (MI355_CFG_STAGE_CLOCKS). */
 int mi355_inflate_seek_last_read_stages(mi355_deflate_ctx* ctx, float ms[4]);
 
+/* ---- BGZF reads: byte ranges of a blocked gzip file from a member index ------------------------------------------
+ * What BGZF exists for, and what htslib's bgzf_useek / bgzf_seek + bgzf_read do: a byte range of the UNCOMPRESSED data, decoding
+ * only the members that hold it, with no output buffer for the rest of the file and -- in the host form -- no copy of the rest.
+ * THE INDEX (mi355_bgzf_index) is an opaque handle that holds the member table -- in_off, in_len, out_off, out_len per member -- in
+ *   HOST memory and nothing on the device.  It is bound to no context: one index serves several contexts or GPUs.
+ *   _index_build[_device]: Path A of the members calls from byte 0 -- find, walk, link on the host, fill, with the kernels and the
+ *     span setting (MI355_CFG_INFLATE_MEMBER_SPAN_BYTES) of mi355_inflate_members -- and NOTHING is decoded.  The run must reach the
+ *     end of the file: a byte that begins no hinted member, or an empty file, is MI355_E_DATA with MI355_VERIFY_FRAME, *idx = NULL and
+ *     report.out_pos = the sum of the ISIZEs in front of it.  MI355_OK: report.out_len = report.out_pos = the total; the report's
+ *     block counts are 0 either way.  The host form stages the file as mi355_inflate_members does and keeps nothing of it.
+ *   _index_from_members: the table mi355_bgzf_encode or a successful mi355_inflate_members returned; no GPU and no context.  The
+ *     table may describe any gzip file of members (MI355_MEMBER_HINTED is not required).  MI355_E_ARG unless n >= 1, every status
+ *     is 0, in_off[0] == 0, in_off[k + 1] == in_off[k] + in_len[k], the last member ends at file_len, out_off[0] == 0,
+ *     out_off[k + 1] == out_off[k] + out_len[k] and every in_len >= 18.
+ *   _index_info: the total, the members, file_len, the host bytes held, the largest out_len.  _index_members: the table (a cap that
+ *     is too small: MI355_E_OUT_TOO_SMALL and *n).  _index_free before nothing in particular: the index owns host memory only.
+ *   WHAT AN INDEX IS: a built index holds the FILE'S OWN CLAIMS -- BSIZE, and ISIZE from the trailers --, as a .gzi does.  A read
+ *     verifies every member it touches and NOTHING about members it does not touch: a lying ISIZE in an untouched member in front
+ *     of a range shifts the range without notice.  An index made from the table of a completed mi355_inflate_members call holds
+ *     verified offsets.
+ *   Virtual offsets (host only; htslib's convention, coffset << 16 | offset inside the member).  _voffset(uoff): for uoff < total
+ *     the member is the one with out_off <= uoff < out_off + out_len (never an empty one); uoff == total gives file_len << 16;
+ *     uoff > total is MI355_E_ARG; a member with out_len > 65536 or in_off >= 2^48 is MI355_E_UNSUPPORTED.  _uoffset(voff): coffset
+ *     must be a member's in_off with the low 16 bits below its out_len (0 is also taken for an empty member); coffset == file_len
+ *     with low bits 0 gives the total; anything else is MI355_E_ARG.  A read at a virtual offset is a read at uoffset(voff).
+ * READS are pread over the uncompressed bytes.  *got = min(len, total - off), 0 when off >= total -- which is MI355_OK, as is
+ *   len == 0.  A range touches member k iff their byte intervals intersect; empty members are never touched.  Every touched member
+ *   is decoded WHOLE by one wave, as a wrapper-2 stream on file[in_off, in_off + in_len) under the cap out_len the index claims, and
+ *   is accepted only if it is structurally clean, exactly out_len bytes long and its CRC-32 and ISIZE match: unlike a seek read the
+ *   checksum IS judged, because members are decoded whole.  Every touched member accepted: MI355_OK, out[0, got) are the bytes; the
+ *   report's block counts are the sums over the touched members, out_len = got, out_pos = off + got.  Otherwise MI355_E_DATA and the
+ *   report is the first failing touched member's in file order: its own status and bit with out_pos = out_off[k] + its out_pos for
+ *   a structural failure inside its claim; MI355_VERIFY_TABLE with out_pos = out_off[k] for a member that is clean but not as long as
+ *   claimed or that inflates beyond its claim; MI355_VERIFY_CHECKSUM with out_pos = out_off[k].  *got = max(out_pos, off) - off
+ *   clipped to len, and out[*got, len) is unspecified.  In every outcome nothing is stored outside [out, out + len).
+ *   A member wanted by exactly one range that covers all of it is decoded in place, straight into out; every other member is decoded
+ *   into a scratch slot of the context's workspace and the wave that decoded it copies the slices asked for.  A member is decoded once
+ *   per call however many ranges want it.  Launch sets hold at most 16384 members and MI355_CFG_INFLATE_GROUP_BYTES of scratch; a
+ *   range that wants a scratch member whose claim exceeds that budget, or any member above 4 GiB - 64 KiB, is MI355_E_UNSUPPORTED
+ *   (status of the range, got 0) -- BGZF never gets there.
+ *   _read_batch_device: got and status are written per range, reports[i] if reports is not NULL; a failing range disturbs no
+ *   neighbour; the call returns the first failing status.  Overlapping out buffers are undefined.  MI355_E_ARG is decided before the
+ *   device is touched (a NULL index, got or report, a NULL out with len > 0, a NULL file of a file_len > 0); a live shard is
+ *   MI355_E_STATE; mi355_deflate_last_info / _last_blocks / _last_batch_info are left alone.  ctx NULL is the default context.
+ *   mi355_bgzf_read (host pointers) copies to the device only the compressed extent from the first through the last touched member,
+ *   and copies back got bytes. */
+typedef struct mi355_bgzf_index mi355_bgzf_index; /* owns: the member table (host) */
+typedef struct {
+    uint64_t total;       /* bytes the file inflates to, as the table claims */
+    uint64_t n_members;
+    uint64_t file_len;
+    uint64_t host_bytes;  /* held by the index */
+    uint64_t max_out_len; /* the largest member's out_len */
+} mi355_bgzf_info; /* 40 bytes */
+int mi355_bgzf_index_build_device(mi355_deflate_ctx* ctx, const void* d_file, size_t file_len, mi355_bgzf_index** idx,
+                                  mi355_inflate_report* report, void* hip_stream);
+int mi355_bgzf_index_build(mi355_deflate_ctx* ctx, const uint8_t* file, size_t file_len, mi355_bgzf_index** idx, mi355_inflate_report* report);
+int mi355_bgzf_index_from_members(const mi355_member_info* members, size_t n, size_t file_len, mi355_bgzf_index** idx);
+void mi355_bgzf_index_free(mi355_bgzf_index* idx);
+int mi355_bgzf_index_info(const mi355_bgzf_index* idx, mi355_bgzf_info* info);
+int mi355_bgzf_index_members(const mi355_bgzf_index* idx, mi355_member_info* out, size_t cap, size_t* n);
+int mi355_bgzf_voffset(const mi355_bgzf_index* idx, uint64_t uoff, uint64_t* voff);
+int mi355_bgzf_uoffset(const mi355_bgzf_index* idx, uint64_t voff, uint64_t* uoff);
+int mi355_bgzf_read_device(mi355_deflate_ctx* ctx, const mi355_bgzf_index* idx, const void* d_file, uint64_t off, uint64_t len, void* d_out,
+                           uint64_t* got, mi355_inflate_report* report, void* hip_stream);
+int mi355_bgzf_read(mi355_deflate_ctx* ctx, const mi355_bgzf_index* idx, const uint8_t* file, uint64_t off, uint64_t len, uint8_t* out,
+                    uint64_t* got, mi355_inflate_report* report);
+int mi355_bgzf_read_batch_device(mi355_deflate_ctx* ctx, const mi355_bgzf_index* idx, const void* d_file, mi355_seek_range* ranges, size_t n,
+                                 mi355_inflate_report* reports /* n entries, or NULL */, void* hip_stream);
+/* Measuring aids and no part of the stable interface.  _last_read: what the context's last BGZF read did -- v[0] distinct members
+ * decoded, v[1] of them in place, v[2] to scratch, v[3] pieces copied, v[4] launch sets, v[5] compressed bytes a host read copied.
+ * _last_read_stages: its HIP-event milliseconds per launch kind summed over the sets -- decode and clip, checksums, trailers; zeros
+ * unless the stage clocks were on (MI355_CFG_STAGE_CLOCKS). */
+int mi355_bgzf_last_read(mi355_deflate_ctx* ctx, uint64_t v[6]);
+int mi355_bgzf_last_read_stages(mi355_deflate_ctx* ctx, float ms[3]);
+
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
  * [parse_lo, parse_hi) (buffer coordinates; parse_lo = 32768 of history except on the first rank,
