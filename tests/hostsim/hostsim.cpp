@@ -59,10 +59,19 @@ void stage_links(Sim& s, const HashOverride& ov) {
     s.link.assign(s.n + 1, 0);
     std::vector<int64_t> head(32768, -1);
     // identity-initialised head table (chained_hash_table.rs:64-69): matters only after a re-warm
-    if (ov.on | ov.m | (uint32_t)g_force_ident)
+    const bool ident = (ov.on | ov.m | (uint32_t)g_force_ident) != 0;
+    if (ident)
         for (int64_t h = 0; h < 32768; h++) head[h] = h;
     HostBytes by{s.in.data()};
     for (uint64_t p = 0; p + 2 < s.n; p++) {
+        // the slide in front of every window from the third on (chained_hash_table.rs:197-219): a bucket whose last entry lies
+        // below the buffer's new start goes back to "the position numbered like the hash", counted from that start (what
+        // k_links_b begins an epoch's table with)
+        if (ident && p >= 2 * (uint64_t)WINDOW_SIZE && p % WINDOW_SIZE == 0) {
+            const int64_t base = (int64_t)(p - WINDOW_SIZE);
+            for (int64_t h = 0; h < 32768; h++)
+                if (head[h] < base) head[h] = base + h;
+        }
         uint32_t h = position_hash(by, p, ov);
         int64_t q = head[h];
         s.link[p] = (q >= 0 && (uint64_t)q < p && p - (uint64_t)q <= WINDOW_SIZE) ? (uint16_t)(p - (uint64_t)q) : 0;

@@ -93,18 +93,21 @@ def common(data, p, q, maxl=MAX_MATCH):
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------------------
-def walk(data, p, checks, prev_length=0, window=WINDOW, maxlen=MAX_MATCH, mutant=None, first=0, filing=None, holes=(), end=None):
+def walk(data, p, checks, prev_length=0, window=WINDOW, maxlen=MAX_MATCH, mutant=None, first=0, filing=None, holes=(), end=None, chain=None):
     """longest_match (matching.rs:87-166) at position p: ((length, distance), visits).  The chain is the earlier positions with
     p's 3-byte hash, nearest first; a visit is dict(rank, q, dist, hit, length): `hit` = the two-byte probe at best - 1, best
     passed, `length` = what was then compared (None without a hit), `best` = the best length the probe stood on.
     first: skip that many chain entries (the far half of a split walk).  mutant: one thing wrong, for the sensitivity tests.
     filing, holes, end (tests/flush_cases.py): the hash every position was filed under where that is not the hash of its own
-    three bytes, positions that were never filed, and the end of the data the encoder had when it looked at p."""
+    three bytes, positions that were never filed, and the end of the data the encoder had when it looked at p.
+    chain (tests/rewarm_cases.py): the positions the walk visits, nearest first, where they are not p's bucket alone -- the bucket
+    and what lies behind the head table's identity entry; window and budget apply to them as to any chain."""
     n = len(data) if end is None else end
     if prev_length >= MAX_MATCH or p + prev_length >= n or p + 2 >= n:
         return (0, 0), []
-    h = _hashes(data) if filing is None else filing
-    chain = np.nonzero(h[:p] == h[p])[0][::-1]
+    if chain is None:
+        h = _hashes(data) if filing is None else filing
+        chain = np.nonzero(h[:p] == h[p])[0][::-1]
     if len(holes):
         chain = np.array([q for q in chain if int(q) not in holes], dtype=np.int64)
     floor = best = max(prev_length, 1)
