@@ -1,7 +1,10 @@
 // What the host drivers of the decode side share (deflate_verify.inc, deflate_inflate.inc, deflate_table_inflate.inc,
-// deflate_index_inflate.inc): the refusal of a context that is busy with a shard, the stream of a call, the staging of a
-// host-buffer call, the descriptor room, the plan of a batch's checksum launches, the stage clocks, and the bookkeeping of a batch
-// entry.  Host code only: the kernels and what they decide are in the four files and their headers.
+// deflate_index_inflate.inc, deflate_members_inflate.inc with deflate_bigmembers_inflate.inc, deflate_seek_inflate.inc with
+// deflate_cut_inflate.inc, deflate_bgzf_read.inc): the head of an entry -- the context, its device, the refusal of a context that is
+// busy with a shard --, the stream of a call, the two halves of the staging of a host-buffer call, the descriptor room, the plan of
+// a batch's checksum launches, the stage clocks, and the bookkeeping of a batch of items and of a batch of ranges.  The decode launch
+// and the checksum half that the IItem drivers share are deflate_inflate.inc's (decode_half, sums_half, framed_tail).  Host code
+// only: the kernels and what they decide are in those files and their headers.
 namespace {
 
 constexpr uint64_t VERIFY_MAX_IN = 0xFFFF0000ull;  // 4 GiB - 64 KiB: what one pass encodes, and what the checksum kernels take
@@ -11,6 +14,17 @@ int shard_refusal(mi355_deflate_ctx* c) {
     if (!c->live_shard) return MI355_OK;
     c->err = "the context holds a sharded encode";
     return MI355_E_STATE;
+}
+
+// The head of a decode entry: the caller's context (a seek read: its handle's) or the default one, which dg keeps for the call; its
+// device selected; shard_refusal.  An entry that refuses its arguments before a context exists calls this behind its checks;
+// args_bad is for the one that looks at them with the context in hand (mi355_inflate), between the device and the shard.
+int decode_enter(mi355_deflate_ctx*& c, DefaultGuard& dg, bool args_bad = false) {
+    c = use_ctx(c, dg);
+    if (!c) return MI355_E_HIP;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (args_bad) return MI355_E_ARG;
+    return shard_refusal(c);
 }
 
 // the caller's stream, or the context's own
@@ -30,27 +44,39 @@ int verify_room(mi355_deflate_ctx* c, size_t bytes) {
     return MI355_OK;
 }
 
-// A call on host buffers around its device worker: the stream goes into the context's staging with a plain copy, the bytes that
-// hold data come back with one.  work(d_stream, d_out, st, &valid): MI355_OK, MI355_E_DATA or MI355_E_OUT_TOO_SMALL and the bytes
-// of d_out that hold data; d_out is nullptr when the caller gave no room.
-template <class Work>
-int staged_call(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, uint8_t* out, size_t out_cap, Work work) {
-    if (const int rc = shard_refusal(c)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
-    if (rc) return rc;
-    rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_cap + 64);
-    if (rc) return rc;
-    hipStream_t st = c->own_stream;
-    if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
-    uint64_t valid = 0;
-    rc = work(c->d_in, out_cap ? c->d_out : nullptr, st, &valid);
+// The staging of a call on host buffers, on the context's own stream, in two halves.  Stage-in: the caller's n bytes on their way
+// into `to` with a plain asynchronous copy; nullptr: into the context's d_in, grown to hold them.
+int stage_in(mi355_deflate_ctx* c, const uint8_t* src, size_t n, uint8_t* to = nullptr) {
+    if (!to) {
+        if (const int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, n + 64)) return rc;
+        to = c->d_in;
+    }
+    if (n) HIPCHK(c, hipMemcpyAsync(to, src, n, hipMemcpyHostToDevice, c->own_stream));
+    return MI355_OK;
+}
+// a call that leaves without having waited on its stream waits here, before the caller may touch the buffer it staged in
+void stage_settle(mi355_deflate_ctx* c) { (void)hipStreamSynchronize(c->own_stream); }  // (the copy of the caller's buffer may be in flight)
+// Stage-out, with the worker's rc: a hard error -- anything but MI355_OK, MI355_E_DATA and MI355_E_OUT_TOO_SMALL, behind which the
+// worker has waited -- settles; else the `valid` bytes of d_out that hold data come back with a plain copy.
+int stage_out(mi355_deflate_ctx* c, int rc, uint8_t* out, uint64_t valid) {
     if (rc != MI355_OK && rc != MI355_E_DATA && rc != MI355_E_OUT_TOO_SMALL) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
+        stage_settle(c);
         return rc;
     }
     if (valid) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)valid, hipMemcpyDeviceToHost));
     return rc;
+}
+
+// A call on host buffers around its device worker, behind decode_enter: room for the output, stage-in, the worker, stage-out.
+// work(d_stream, d_out, st, &valid): MI355_OK, MI355_E_DATA or MI355_E_OUT_TOO_SMALL and the bytes of d_out that hold data; d_out
+// is nullptr when the caller gave no room.
+template <class Work>
+int staged_call(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, uint8_t* out, size_t out_cap, Work work) {
+    if (const int rc = ensure_buf(c, &c->d_out, &c->d_out_cap, out_cap + 64)) return rc;
+    if (const int rc = stage_in(c, stream, stream_len)) return rc;
+    uint64_t valid = 0;
+    const int rc = work(c->d_in, out_cap ? c->d_out : nullptr, c->own_stream, &valid);
+    return stage_out(c, rc, out, valid);
 }
 
 // Where a batched call keeps its checksum plan in the descriptor room, behind `front` bytes of its own descriptors and in front of
@@ -165,6 +191,29 @@ int batch_give(mi355_batch_item* items, const std::vector<uint32_t>& act, Report
             char what[48];
             snprintf(what, sizeof what, "%s: item %u", name, act[j]);
             say(r, s, what);
+        }
+    }
+    return first;
+}
+
+// The tail of a batch of ranges, which skips none: judge(i, report, &got) turns what the call knows of range i into its report, the
+// bytes it got and its status; every report gets the call's time; the first failure is the call's return code and, through
+// say(report, status, what) with what = "<name>: range <index in the caller's array>", its text.
+template <class Judge, class Say>
+int ranges_give(mi355_seek_range* r, size_t n, mi355_inflate_report* reports, float ms, const char* name, Judge judge, Say say) {
+    int first = MI355_OK;
+    for (size_t i = 0; i < n; i++) {
+        mi355_inflate_report rep{};
+        uint64_t got = 0;
+        const int s = judge(i, rep, &got);
+        rep.ms = ms;
+        r[i].got = got, r[i].status = s, r[i].reserved = 0;
+        if (reports) reports[i] = rep;
+        if (s != MI355_OK && first == MI355_OK) {
+            first = s;
+            char what[48];
+            snprintf(what, sizeof what, "%s: range %zu", name, i);
+            say(rep, s, what);
         }
     }
     return first;

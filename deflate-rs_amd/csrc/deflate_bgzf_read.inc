@@ -5,8 +5,9 @@
 //                 buffer for a member in place, else a scratch slot of the workspace --, then the member's pieces from the slot to
 //                 the ranges that asked for them, then the record
 // The index is built by the find, walk and fill kernels of deflate_members_inflate.inc as they stand, and the members' checksums are
-// judged by the batch plan and k_inflate_trailer of deflate_inflate.inc.  A launch set has two waits: the records, then the
-// trailers.  Nothing waits inside a kernel.  DESIGN.md section 19.
+// judged by the batch plan and k_inflate_trailer of deflate_inflate.inc: a launch set is that file's decode_half with k_bgzf_read
+// and sums_half, so it has two waits: the records, then the trailers.  Nothing waits inside a kernel.  The entries' head, the
+// staging of the host forms and the ranges' tail are decode_host.inc's.  DESIGN.md section 19.
 #include "bgzf_read.h"
 
 namespace mi355 {
@@ -125,35 +126,26 @@ int bgzf_read_ranges(mi355_deflate_ctx* c, const br::Index& ix, const uint8_t* d
             href[j] = d.ref;
         }
         if (np) memcpy(c->v_host + piece_at, s.pieces.data(), sizeof(br::Piece) * np);
-        iw::Rec* hrec = reinterpret_cast<iw::Rec*>(c->v_host + plan.rec_at);
-        HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, front, hipMemcpyHostToDevice, st));
-        HIPCHK(c, clk.mark(0));
-        hipLaunchKernelGGL(k_bgzf_read, dim3((uint32_t)k), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
-                           reinterpret_cast<const br::Ref*>(c->v_dev + ref_at), reinterpret_cast<const br::Piece*>(c->v_dev + piece_at),
-                           reinterpret_cast<iw::Rec*>(c->v_dev + plan.rec_at));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.mark(1));
-        HIPCHK(c, hipMemcpyAsync(hrec, c->v_dev + plan.rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));  // the first wait of a set: the records
+        const iw::Rec* hrec = reinterpret_cast<const iw::Rec*>(c->v_host + plan.rec_at);
+        // the first half and wait of a set: inflate_run's (decode_half of deflate_inflate.inc), with this file's kernel and its two arrays
+        rc = decode_half(
+            c, st, k, front, plan.rec_at,
+            [&](const IItem* items, iw::Rec* d_recs) {
+                hipLaunchKernelGGL(k_bgzf_read, dim3((uint32_t)k), dim3(64), 0, st, items, reinterpret_cast<const br::Ref*>(c->v_dev + ref_at),
+                                   reinterpret_cast<const br::Piece*>(c->v_dev + piece_at), d_recs);
+            },
+            [&](int e) { return clk.mark(e); });
+        if (rc) return rc;
         clk.lap(0, 1, 0);
+        // the second half and wait (sums_half): the members that are clean and fit get their sums, the items go up again with the plan
         size_t summed = 0;
         for (size_t j = 0; j < k; j++)
             if (br::br_summed<br::Rules>(hrec[j], hit[j].cap)) hit[j].sc = &plan.states(c)[j].sc, summed++;
-        if (summed) {  // the second half: the batch's checksum plan over the slots of the members that are clean and fit, the trailers
-            rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* len) { *p = hit[j].out, *len = hit[j].sc ? hit[j].cap : 0; });
+        if (summed) {
+            rc = sums_half(
+                c, st, plan, 2, false, 0, false, [&](size_t j, uint64_t* len) { return *len = hit[j].cap, hit[j].sc != nullptr; },
+                [&](int e) { return clk.mark(e == 0 ? 2 : e == 2 ? 3 : 4); });  // (events 2 to 4: the checksums, the trailers)
             if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, plan.st_at, hipMemcpyHostToDevice, st));
-            HIPCHK(c, clk.mark(2));
-            rc = plan.launch(c, 2, st);
-            if (rc) return rc;
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, clk.mark(3));
-            hipLaunchKernelGGL(k_inflate_trailer, dim3(cdiv(k, 64)), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
-                               reinterpret_cast<iw::Rec*>(c->v_dev + plan.rec_at), (uint32_t)k);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, clk.mark(4));
-            HIPCHK(c, hipMemcpyAsync(hrec, c->v_dev + plan.rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));  // the second wait: the trailers
             clk.lap(2, 3, 1), clk.lap(3, 4, 2);
         }
         for (size_t j = 0; j < k; j++) ids.push_back(s.decs[j].member), recs.push_back(hrec[j]);
@@ -161,33 +153,24 @@ int bgzf_read_ranges(mi355_deflate_ctx* c, const br::Index& ix, const uint8_t* d
     const uint64_t v[6] = {cnt.distinct, cnt.in_place, cnt.scratch, cnt.pieces, cnt.sets, copied};
     for (int k = 0; k < 6; k++) c->br_stats[k] = v[k];
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    int first = MI355_OK;
-    for (size_t i = 0; i < n; i++) {
-        mi355_inflate_report rep{};
-        uint64_t got = 0;
-        int rc = MI355_E_UNSUPPORTED;
-        if (!unsupported[i])
-            rc = br::br_give(ix, ranges[i],
-                             [&](uint64_t member, const iw::Rec*& rec, br::Verdict& vd) {
-                                 const size_t at = std::lower_bound(ids.begin(), ids.end(), member) - ids.begin();
-                                 rec = &recs[at];  // (there: the plan decoded every member a supported range touches)
-                                 vd = br::br_judge<br::Rules>(recs[at], ix.mem[member].out_len);
-                             },
-                             rep, &got);
-        rep.ms = ms;
-        r[i].got = got, r[i].status = rc, r[i].reserved = 0;
-        if (reports) reports[i] = rep;
-        if (rc != MI355_OK && first == MI355_OK) {
-            first = rc;
-            char what[48];
-            snprintf(what, sizeof what, "bgzf read: range %zu", i);
+    return ranges_give(
+        r, n, reports, ms, "bgzf read",
+        [&](size_t i, mi355_inflate_report& rep, uint64_t* got) -> int {
+            if (unsupported[i]) return MI355_E_UNSUPPORTED;
+            return br::br_give(ix, ranges[i],
+                               [&](uint64_t member, const iw::Rec*& rec, br::Verdict& vd) {
+                                   const size_t at = std::lower_bound(ids.begin(), ids.end(), member) - ids.begin();
+                                   rec = &recs[at];  // (there: the plan decoded every member a supported range touches)
+                                   vd = br::br_judge<br::Rules>(recs[at], ix.mem[member].out_len);
+                               },
+                               rep, got);
+        },
+        [&](const mi355_inflate_report& rep, int rc, const char* what) {
             if (rc == MI355_E_DATA)
                 inflate_say(c, rep, rc, what);
             else
                 c->err = std::string(what) + ": a member's claim exceeds what one launch set takes";
-        }
-    }
-    return first;
+        });
 }
 
 bool bgzf_ranges_bad(const mi355_bgzf_index* h, const void* file, const mi355_seek_range* r, size_t n) {
@@ -206,10 +189,7 @@ int mi355_bgzf_index_build_device(mi355_deflate_ctx* c, const void* d_file, size
     if (!idx || !report || (!d_file && file_len)) return tabled_refuse(c, "bgzf index: bad argument");
     *idx = nullptr;
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return bgzf_index_one(c, reinterpret_cast<const uint8_t*>(d_file), file_len, idx, report, call_stream(c, hip_stream));
 }
 
@@ -218,15 +198,10 @@ int mi355_bgzf_index_build(mi355_deflate_ctx* c, const uint8_t* file, size_t fil
     if (!idx || !report || (!file && file_len)) return tabled_refuse(c, "bgzf index: bad argument");
     *idx = nullptr;
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
-    if (const int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, file_len + 64)) return rc;
-    hipStream_t st = c->own_stream;
-    if (file_len) HIPCHK(c, hipMemcpyAsync(c->d_in, file, file_len, hipMemcpyHostToDevice, st));
-    const int rc = bgzf_index_one(c, c->d_in, file_len, idx, report, st);
-    (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
+    if (const int rc = decode_enter(c, dg_)) return rc;
+    if (const int rc = stage_in(c, file, file_len)) return rc;
+    const int rc = bgzf_index_one(c, c->d_in, file_len, idx, report, c->own_stream);
+    stage_settle(c);  // (on every path: behind a worker that has waited it finds the stream idle)
     return rc;
 }
 
@@ -269,10 +244,7 @@ int mi355_bgzf_read_batch_device(mi355_deflate_ctx* c, const mi355_bgzf_index* h
                                  mi355_inflate_report* reports, void* hip_stream) {
     if (bgzf_ranges_bad(h, d_file, r, n)) return tabled_refuse(c, "bgzf read: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return bgzf_read_ranges(c, h->ix, reinterpret_cast<const uint8_t*>(d_file), 0, r, n, reports, call_stream(c, hip_stream), 0);
 }
 
@@ -290,10 +262,7 @@ int mi355_bgzf_read(mi355_deflate_ctx* c, const mi355_bgzf_index* h, const uint8
                     uint64_t* got, mi355_inflate_report* report) {
     if (!h || !got || !report || (!out && len) || (!file && h->ix.file_len)) return tabled_refuse(c, "bgzf read: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     const br::Index& ix = h->ix;
     const uint64_t room = br::br_got(off, len, ix.total);
     uint64_t lo = 0, hi = 0;
@@ -302,18 +271,12 @@ int mi355_bgzf_read(mi355_deflate_ctx* c, const mi355_bgzf_index* h, const uint8
         br::br_touched(ix, off, room, k0, k1);
         lo = ix.mem[k0].in_off, hi = ix.mem[k1].in_off + ix.mem[k1].in_len;
     }
-    if (const int rc = ensure_buf(c, &c->d_in, &c->d_in_cap, (size_t)(hi - lo) + 64)) return rc;
     if (const int rc = ensure_buf(c, &c->d_out, &c->d_out_cap, (size_t)room + 64)) return rc;
-    hipStream_t st = c->own_stream;
-    if (hi > lo) HIPCHK(c, hipMemcpyAsync(c->d_in, file + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+    if (const int rc = stage_in(c, file + lo, (size_t)(hi - lo))) return rc;
     mi355_seek_range r{off, room, c->d_out, 0, MI355_OK, 0u};
-    const int rc = bgzf_read_ranges(c, ix, c->d_in, lo, &r, 1, report, st, hi - lo);
-    if (rc != MI355_OK && rc != MI355_E_DATA) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
-        return rc;
-    }
-    if (r.got) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)r.got, hipMemcpyDeviceToHost));
-    *got = r.got;
+    int rc = bgzf_read_ranges(c, ix, c->d_in, lo, &r, 1, report, c->own_stream, hi - lo);
+    rc = stage_out(c, rc, out, r.got);
+    if (rc == MI355_OK || rc == MI355_E_DATA) *got = r.got;
     return rc;
 }
 

@@ -137,11 +137,8 @@ int mi355_inflate_index_device(mi355_deflate_ctx* c, const void* d_stream, size_
                                size_t* n_blocks, mi355_inflate_report* report, void* hip_stream) {
     if (inflate_args_bad(d_stream, stream_len, wrapper, blocks, cap, n_blocks, report)) return tabled_refuse(c, "inflate index: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
     std::vector<mi355_block_info> table;
     iw::Rec acc;
     if (const int rc = index_run(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, call_stream(c, hip_stream), table, acc))
@@ -149,28 +146,18 @@ int mi355_inflate_index_device(mi355_deflate_ctx* c, const void* d_stream, size_
     return index_give(c, table, acc, blocks, cap, n_blocks, report, t0);
 }
 
-// host buffers: the stream into the context's staging; no output buffer and a table to hand back: not the shape of staged_call
+// host buffers: the stream staged in; no output buffer and a table to hand back, so stage-out only for an error of index_run's,
+// all of which are hard
 int mi355_inflate_index(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, mi355_block_info* blocks, size_t cap,
                         size_t* n_blocks, mi355_inflate_report* report) {
     if (inflate_args_bad(stream, stream_len, wrapper, blocks, cap, n_blocks, report)) return tabled_refuse(c, "inflate index: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = shard_refusal(c);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_buf(c, &c->d_in, &c->d_in_cap, stream_len + 64);
-    if (rc) return rc;
-    hipStream_t st = c->own_stream;
-    if (stream_len) HIPCHK(c, hipMemcpyAsync(c->d_in, stream, stream_len, hipMemcpyHostToDevice, st));
+    if (const int rc = stage_in(c, stream, stream_len)) return rc;
     std::vector<mi355_block_info> table;
     iw::Rec acc;
-    rc = index_run(c, c->d_in, stream_len, wrapper, st, table, acc);
-    if (rc) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
-        return rc;
-    }
+    if (const int rc = index_run(c, c->d_in, stream_len, wrapper, c->own_stream, table, acc)) return stage_out(c, rc, nullptr, 0);
     return index_give(c, table, acc, blocks, cap, n_blocks, report, t0);
 }
 
@@ -178,10 +165,7 @@ int mi355_inflate_parallel_device(mi355_deflate_ctx* c, const void* d_stream, si
                                   size_t* out_len, mi355_inflate_report* report, void* hip_stream) {
     if (inflate_args_bad(d_stream, stream_len, wrapper, d_out, out_cap, out_len, report)) return tabled_refuse(c, "inflate: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     uint64_t valid = 0;
     return parallel_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, reinterpret_cast<uint8_t*>(d_out), out_cap, out_len,
                         report, call_stream(c, hip_stream), &valid);
@@ -192,8 +176,7 @@ int mi355_inflate_parallel(mi355_deflate_ctx* c, const uint8_t* stream, size_t s
                            size_t* out_len, mi355_inflate_report* report) {
     if (inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report)) return tabled_refuse(c, "inflate: bad argument");
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
         return parallel_one(c, d_stream, stream_len, wrapper, d_out, out_cap, out_len, report, st, valid);
     });

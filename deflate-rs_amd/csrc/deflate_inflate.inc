@@ -2,7 +2,9 @@
 // bytes in device memory.  k_inflate runs inflate_write.h as one wave per stream -- the scalar chain of k_verify with the lanes
 // storing where verify's compare -- and, for a framed stream, the checksum kernels of the encode run over the OUTPUT afterwards and
 // k_inflate_trailer compares them with the trailer.  tests/inflwrite/ builds the same text for the host.  The host driver's shared
-// steps are in decode_host.inc.  DESIGN.md section 12.
+// steps are in decode_host.inc; the two halves of a decode over IItems -- decode_half: upload, a kernel of one wave per item, records
+// back, wait; sums_half: the checksum launches and framed_tail, the one place k_inflate_trailer is launched from -- are here, and the
+// members and BGZF-read drivers call them too.  DESIGN.md section 12.
 #include "inflate_write.h"
 
 namespace mi355 {
@@ -85,13 +87,14 @@ bool inflate_args_bad(const void* stream, size_t stream_len, int wrapper, const 
 }
 
 // The end of a framed call, around the checksum launches over the outputs that are clean and fit (sums()): k_inflate_trailer over the
-// k records at rec_at of the descriptor room, whose items are at its front, the records back, the wait.  mark(0) and mark(1) stand
-// around the launches (the tabled driver's stage clock).
+// k records at rec_at of the descriptor room, whose items are at its front, the records back, the wait.  The stage clock of a
+// caller that keeps one: mark(0) in front of the checksum launches, mark(2) between them and k_inflate_trailer, mark(1) behind it.
 template <class Sums, class Mark>
 int framed_tail(mi355_deflate_ctx* c, hipStream_t st, size_t k, size_t rec_at, Sums sums, Mark mark) {
     HIPCHK(c, mark(0));
     const int rc = sums();
     if (rc) return rc;
+    HIPCHK(c, mark(2));
     hipLaunchKernelGGL(k_inflate_trailer, dim3(cdiv(k, 64)), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
                        reinterpret_cast<iw::Rec*>(c->v_dev + rec_at), (uint32_t)k);
     HIPCHK(c, hipGetLastError());
@@ -100,16 +103,66 @@ int framed_tail(mi355_deflate_ctx* c, hipStream_t st, size_t k, size_t rec_at, S
     HIPCHK(c, hipStreamSynchronize(st));
     return MI355_OK;
 }
+const auto no_mark = [](int) { return hipSuccess; };
 
-// k streams, device resident.  The decode launch, the records back (the one wait of a raw call); framed: the checksum launches over
-// the outputs that are clean and fit -- `one`: launch_sums_one into the context's scalars, else the batch's plan over one flat grid
-// --, and framed_tail.  fill(j, item): the j-th stream.  The records are left in c->v_host, *recs_out.
+// The first half of a decode over IItems: the caller's k items at the front of the descriptor room -- and what else of its
+// descriptors lies in the first `front` bytes -- go up, launch(items, records) starts a kernel of one wave per item between mark(0)
+// and mark(1), the k records at rec_at come back, the wait.  They are left in c->v_host.
+template <class Launch, class Mark>
+int decode_half(mi355_deflate_ctx* c, hipStream_t st, size_t k, size_t front, size_t rec_at, Launch launch, Mark mark) {
+    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, front, hipMemcpyHostToDevice, st));
+    HIPCHK(c, mark(0));
+    launch(reinterpret_cast<const IItem*>(c->v_dev), reinterpret_cast<iw::Rec*>(c->v_dev + rec_at));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, mark(1));
+    HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return MI355_OK;
+}
+// k_inflate as decode_half's launch
+auto inflate_launch(size_t k, hipStream_t st) {
+    return [=](const IItem* items, iw::Rec* recs) { hipLaunchKernelGGL(k_inflate, dim3((uint32_t)k), dim3(64), 0, st, items, recs); };
+}
+
+// The second half, of a framed call, once the outputs' lengths are known: the checksum launches over the outputs that are clean
+// and fit, and framed_tail.  The plan's k items are at the front of c->v_host and their records at plan.rec_at.  judged(j, &n): is
+// item j's checksum judged, and over how many bytes of its out.  None judged: nothing is launched; one longer than the checksum
+// kernels take: MI355_E_UNSUPPORTED.  `one`: launch_sums_one into the context's scalars, else the batch's plan over one flat grid,
+// uploaded with what lies from `from` in front of it (0: the items again, their sc decided since the first half); recs_up: the
+// records too, for a caller whose decode was not the launch in front (a members call).  mark: framed_tail's.
+template <class Judged, class Mark>
+int sums_half(mi355_deflate_ctx* c, hipStream_t st, const BatchSums& plan, int wrapper, bool one, size_t from, bool recs_up, Judged judged,
+              Mark mark) {
+    const IItem* hit = reinterpret_cast<const IItem*>(c->v_host);
+    size_t n_judged = 0;
+    uint64_t n = 0, n0 = 0;
+    for (size_t j = 0; j < plan.k; j++)
+        if (judged(j, &n)) {
+            if (n > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;  // (what the checksum kernels take)
+            if (!j) n0 = n;
+            n_judged++;
+        }
+    if (!n_judged) return MI355_OK;
+    if (!one) {
+        const int rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* len) {
+            *p = hit[j].out;
+            if (!judged(j, len)) *len = 0;
+        });
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->v_dev + from, c->v_host + from, plan.st_at - from, hipMemcpyHostToDevice, st));
+    }
+    if (recs_up)
+        HIPCHK(c, hipMemcpyAsync(c->v_dev + plan.rec_at, c->v_host + plan.rec_at, sizeof(iw::Rec) * plan.k, hipMemcpyHostToDevice, st));
+    return framed_tail(c, st, plan.k, plan.rec_at, [&]() { return one ? launch_sums_one(c, st, wrapper, hit[0].out, n0) : plan.launch(c, wrapper, st); },
+                       mark);
+}
+
+// k streams, device resident: the two halves in sequence, the second for a framed call.  fill(j, item): the j-th stream.  The
+// records are left in c->v_host, *recs_out.
 template <class Fill>
 int inflate_run(mi355_deflate_ctx* c, size_t k, int wrapper, bool one, hipStream_t st, Fill fill, const iw::Rec** recs_out) {
     // [IItem k] and, for a framed batch, the checksum plan behind them
-    const bool batch_sums = wrapper && !one;
-    const BatchSums plan(sizeof(IItem) * k, k, batch_sums, sizeof(iw::Rec));
-    const size_t rec_at = plan.rec_at;
+    const BatchSums plan(sizeof(IItem) * k, k, wrapper && !one, sizeof(iw::Rec));
     int rc = verify_room(c, plan.bytes);
     if (rc) return rc;
     IItem* hit = reinterpret_cast<IItem*>(c->v_host);
@@ -118,35 +171,13 @@ int inflate_run(mi355_deflate_ctx* c, size_t k, int wrapper, bool one, hipStream
         hit[j].sc = !wrapper ? nullptr : one ? c->d_sc : &plan.states(c)[j].sc;
         hit[j].wrapper = (uint32_t)wrapper, hit[j].pad = 0;
     }
-    const iw::Rec* recs = reinterpret_cast<const iw::Rec*>(c->v_host + rec_at);
+    const iw::Rec* recs = reinterpret_cast<const iw::Rec*>(c->v_host + plan.rec_at);
     *recs_out = recs;
-    HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, plan.bat_at, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_inflate, dim3((uint32_t)k), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
-                       reinterpret_cast<iw::Rec*>(c->v_dev + rec_at));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->v_host + rec_at, c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (!wrapper) return MI355_OK;
-    // the second half of a framed call: the output's length is known now
-    size_t judged = 0;
-    for (size_t j = 0; j < k; j++)
-        if (iw::iw_judged(recs[j], (uint32_t)wrapper, hit[j].cap)) {
-            if (recs[j].out_len > VERIFY_MAX_IN) return MI355_E_UNSUPPORTED;  // (what the checksum kernels take)
-            judged++;
-        }
-    if (!judged) return MI355_OK;
-    return framed_tail(
-        c, st, k, rec_at,
-        [&]() {
-            if (one) return launch_sums_one(c, st, wrapper, hit[0].out, recs[0].out_len);
-            const int rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* n) {
-                *p = hit[j].out, *n = iw::iw_judged(recs[j], (uint32_t)wrapper, hit[j].cap) ? recs[j].out_len : 0;
-            });
-            if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->v_dev + plan.bat_at, c->v_host + plan.bat_at, plan.st_at - plan.bat_at, hipMemcpyHostToDevice, st));
-            return plan.launch(c, wrapper, st);
-        },
-        [](int) { return hipSuccess; });
+    rc = decode_half(c, st, k, plan.bat_at, plan.rec_at, inflate_launch(k, st), no_mark);
+    if (rc || !wrapper) return rc;
+    return sums_half(
+        c, st, plan, wrapper, one, plan.bat_at, false,
+        [&](size_t j, uint64_t* n) { return *n = recs[j].out_len, iw::iw_judged(recs[j], (uint32_t)wrapper, hit[j].cap); }, no_mark);
 }
 
 // one stream, device resident, its arguments checked by the entry; *valid: the bytes of d_out that hold data
@@ -171,11 +202,7 @@ extern "C" {
 int mi355_inflate_device(mi355_deflate_ctx* c, const void* d_stream, size_t stream_len, int wrapper, void* d_out, size_t out_cap,
                          size_t* out_len, mi355_inflate_report* report, void* hip_stream) {
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (inflate_args_bad(d_stream, stream_len, wrapper, d_out, out_cap, out_len, report)) return MI355_E_ARG;
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_, inflate_args_bad(d_stream, stream_len, wrapper, d_out, out_cap, out_len, report))) return rc;
     uint64_t valid = 0;
     return inflate_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, reinterpret_cast<uint8_t*>(d_out), out_cap, out_len,
                        report, call_stream(c, hip_stream), &valid);
@@ -185,9 +212,7 @@ int mi355_inflate_device(mi355_deflate_ctx* c, const void* d_stream, size_t stre
 int mi355_inflate(mi355_deflate_ctx* c, const uint8_t* stream, size_t stream_len, int wrapper, uint8_t* out, size_t out_cap, size_t* out_len,
                   mi355_inflate_report* report) {
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    if (inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report)) return MI355_E_ARG;
+    if (const int rc = decode_enter(c, dg_, inflate_args_bad(stream, stream_len, wrapper, out, out_cap, out_len, report))) return rc;
     return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
         return inflate_one(c, d_stream, stream_len, wrapper, d_out, out_cap, out_len, report, st, valid);
     });

@@ -6,7 +6,7 @@
 //   k_member_fill    one lane per walker on the chain: the (offset, size, ISIZE) rows of its members
 //   k_inflate_chain  one workgroup of one wave: member after member, open ended (Path B)
 // The hinted members themselves are decoded by k_inflate as it stands, and the members' checksums by the batch plan and
-// k_inflate_trailer of deflate_inflate.inc.  A large member that states no size is found and decoded in parallel by the kernels of
+// k_inflate_trailer of deflate_inflate.inc, through that file's decode_half and sums_half.  A large member that states no size is found and decoded in parallel by the kernels of
 // deflate_bigmembers_inflate.inc, which MemberDev::chain drives (inflate_bigmembers.h).  Nothing waits inside a kernel.  The host
 // driver's shared steps are in decode_host.inc.  DESIGN.md section 15.
 #include "inflate_members.h"
@@ -132,12 +132,9 @@ struct MemberDev {
         HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows, sizeof(im::Hint) * n_rows, hipMemcpyDeviceToHost, st));
         return wait(2);
     }
-    // k members as their rows claim them, the first at output position p: the batched launch of k_inflate, wrapper 2, no sums yet.
-    // KEEP IN STEP with inflate_run (deflate_inflate.inc): decode() is its first half -- the IItem array at the front of the descriptor
-    // room, the records at a 256-byte boundary behind it, upload, k_inflate a workgroup per item, records back -- and sums() below
-    // its second half -- the judged count, the VERIFY_MAX_IN test, plan.fill, the plan's upload, framed_tail.  They are apart here
-    // because the checksums of a members call are judged once over the whole table, after Path B has had its say, and not per launch;
-    // a change to IItem, to BatchSums' layout or to what inflate_run uploads has to be made in both places.
+    // k members as their rows claim them, the first at output position p: inflate_run's first half (decode_half of
+    // deflate_inflate.inc) with k_inflate, wrapper 2, no sums yet.  Its second half is sums() below: the two are apart here because
+    // the checksums of a members call are judged once over the whole table, after Path B has had its say, and not per launch.
     int decode(const im::Hint* rows, uint64_t k, uint64_t p, std::vector<iw::Rec>& got) {
         const size_t rec_at = align_up(sizeof(IItem) * k, 256);
         if (const int rc = verify_room(c, rec_at + sizeof(iw::Rec) * k)) return rc;
@@ -150,15 +147,11 @@ struct MemberDev {
                            nullptr, 2u, 0u};
             p += h.isize;
         }
-        HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, sizeof(IItem) * k, hipMemcpyHostToDevice, st));
-        HIPCHK(c, clk.mark(0));
-        hipLaunchKernelGGL(k_inflate, dim3((uint32_t)k), dim3(64), 0, st, reinterpret_cast<const IItem*>(c->v_dev),
-                           reinterpret_cast<iw::Rec*>(c->v_dev + rec_at));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, clk.mark(1));
-        got.resize(k);
-        HIPCHK(c, hipMemcpyAsync(got.data(), c->v_dev + rec_at, sizeof(iw::Rec) * k, hipMemcpyDeviceToHost, st));
-        return wait(3);
+        if (const int rc = decode_half(c, st, k, sizeof(IItem) * k, rec_at, inflate_launch(k, st), [&](int e) { return clk.mark(e); })) return rc;
+        clk.lap(0, 1, 3);
+        const iw::Rec* recs = reinterpret_cast<const iw::Rec*>(c->v_host + rec_at);
+        got.assign(recs, recs + k);
+        return MI355_OK;
     }
     // Path B from (o, p): by discovery and the joint tabled launch sets when enough of the file is left, else -- and for what those
     // leave -- by the one wave
@@ -279,20 +272,12 @@ struct MemberDev {
     }
     // The checksum pass over the member table: the batch plan's flat CRC launch over the outputs of the judged members, then
     // k_inflate_trailer against their trailers, MEMBER_GROUP members a turn; it stops behind the first turn that holds a failure.
-    // (The second half of inflate_run, see decode(): the items here carry no decode, sc == nullptr marks a member that is not judged.)
+    // (inflate_run's second half, sums_half, a turn: the items here carry no decode, sc == nullptr marks a member that is not judged,
+    // and the records go up with the plan.)
     int sums(const std::vector<im::Member>& mem, std::vector<iw::Rec>& recs) {
         for (size_t lo = 0; lo < mem.size(); lo += MEMBER_GROUP) {
             const size_t k = mem.size() - lo < MEMBER_GROUP ? mem.size() - lo : MEMBER_GROUP;
-            size_t judged = 0;
-            for (size_t j = 0; j < k; j++)
-                if (im::im_judged(mem[lo + j], out_cap)) {
-                    if (mem[lo + j].out_len > VERIFY_MAX_IN) {
-                        c->err = "inflate members: a member inflates to more than 4 GiB - 64 KiB";
-                        return MI355_E_UNSUPPORTED;
-                    }
-                    judged++;
-                }
-            if (!judged) continue;
+            if (std::none_of(mem.begin() + lo, mem.begin() + lo + k, [&](const im::Member& m) { return im::im_judged(m, out_cap); })) continue;
             const BatchSums plan(sizeof(IItem) * k, k, true, sizeof(iw::Rec));
             if (const int rc = verify_room(c, plan.bytes)) return rc;
             IItem* hit = reinterpret_cast<IItem*>(c->v_host);
@@ -303,12 +288,11 @@ struct MemberDev {
                                on ? &plan.states(c)[j].sc : nullptr, 2u, 0u};
             }
             memcpy(c->v_host + plan.rec_at, recs.data() + lo, sizeof(iw::Rec) * k);
-            if (const int rc = plan.fill(c, [&](size_t j, const uint8_t** p, uint64_t* len) { *p = hit[j].out, *len = hit[j].sc ? hit[j].cap : 0; }))
-                return rc;
-            HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, plan.st_at, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->v_dev + plan.rec_at, c->v_host + plan.rec_at, sizeof(iw::Rec) * k, hipMemcpyHostToDevice, st));
-            if (const int rc = framed_tail(c, st, k, plan.rec_at, [&]() { return plan.launch(c, 2, st); }, [&](int e) { return clk.mark(e); }))
-                return rc;
+            const int rc = sums_half(
+                c, st, plan, 2, false, 0, true, [&](size_t j, uint64_t* n) { return *n = hit[j].cap, hit[j].sc != nullptr; },
+                [&](int e) { return e < 2 ? clk.mark(e) : hipSuccess; });  // (one slot for the checksums and the trailers)
+            if (rc == MI355_E_UNSUPPORTED) c->err = "inflate members: a member inflates to more than 4 GiB - 64 KiB";
+            if (rc) return rc;
             clk.lap(0, 1, 5);
             memcpy(recs.data() + lo, c->v_host + plan.rec_at, sizeof(iw::Rec) * k);
             for (size_t j = 0; j < k; j++)
@@ -387,10 +371,7 @@ int mi355_inflate_members_device(mi355_deflate_ctx* c, const void* d_stream, siz
     if (members_args_bad(d_stream, stream_len, d_out, out_cap, out_len, members, members_cap, report))
         return members_refuse(c);
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     uint64_t valid = 0;
     return members_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, reinterpret_cast<uint8_t*>(d_out), out_cap, out_len, members,
                        members_cap, n_members, report, call_stream(c, hip_stream), &valid);
@@ -402,8 +383,7 @@ int mi355_inflate_members(mi355_deflate_ctx* c, const uint8_t* stream, size_t st
     if (members_args_bad(stream, stream_len, out, out_cap, out_len, members, members_cap, report))
         return members_refuse(c);
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
         return members_one(c, d_stream, stream_len, d_out, out_cap, out_len, members, members_cap, n_members, report, st, valid);
     });

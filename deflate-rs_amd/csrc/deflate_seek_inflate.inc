@@ -9,7 +9,8 @@
 //   k_inflate_seek_resolve  pass 3, flat over the set's symbols -- the only kernel that writes `out`, and only [lo, min(limit, cap))
 // The build is the tabled inflate's passes 1 and 2 (k_inflate_tab, k_inflate_tab_window) group by group without an output buffer; a
 // framed stream's groups are resolved into a scratch region for the checksum launches.  The host driver's shared steps are in
-// decode_host.inc.  DESIGN.md section 16.
+// decode_host.inc: the entries' head (a read takes its context from the handle), the stage-in of a host build into the buffer the
+// handle keeps, the stage-out of a host read, and the tail of a batch of ranges.  DESIGN.md section 16.
 // With MI355_CFG_INFLATE_SEEK_CUT_BYTES set at the build, the handle also keeps CUTS inside its entries (inflate_cut.h; the kernels are
 // deflate_cut_inflate.inc's): the build's pass 1 is k_inflate_tab_cut, and a read's pass 1 is k_inflate_cut over cuts with
 // k_inflate_cut_flatten behind it -- four launches a set -- in front of the same passes 2 and 3.  DESIGN.md section 17.
@@ -429,23 +430,14 @@ int seek_read_ranges(mi355_inflate_seek* h, mi355_deflate_ctx* c, const uint8_t*
             if (!failed[pt.range] && !is::is_report(recs, pt, acc[pt.range])) failed[pt.range] = 1;
     }
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    int first = MI355_OK;
-    for (size_t i = 0; i < n; i++) {
-        r[i].got = is::is_give(acc[i], r[i].off, r[i].len, h->total);
-        mi355_inflate_report rep;
-        uint64_t valid = 0;
-        const int rc = inflate_rc(iw::iw_report(acc[i], ~0ull, rep, &valid));
-        rep.ms = ms;
-        r[i].status = rc, r[i].reserved = 0;
-        if (reports) reports[i] = rep;
-        if (rc != MI355_OK && first == MI355_OK) {
-            first = rc;
-            char what[48];
-            snprintf(what, sizeof what, "inflate seek: range %zu", i);
-            inflate_say(c, rep, rc, what);
-        }
-    }
-    return first;
+    return ranges_give(
+        r, n, reports, ms, "inflate seek",
+        [&](size_t i, mi355_inflate_report& rep, uint64_t* got) {
+            *got = is::is_give(acc[i], r[i].off, r[i].len, h->total);
+            uint64_t valid = 0;
+            return inflate_rc(iw::iw_report(acc[i], ~0ull, rep, &valid));
+        },
+        [&](const mi355_inflate_report& rep, int rc, const char* what) { inflate_say(c, rep, rc, what); });
 }
 
 bool seek_ranges_bad(const mi355_inflate_seek* h, const mi355_seek_range* r, size_t n) {
@@ -465,10 +457,7 @@ int mi355_inflate_seek_build_device(mi355_deflate_ctx* c, const void* d_stream, 
     if (const char* why = seek_build_args(d_stream, stream_len, wrapper, blocks, n_blocks, spacing, seek, report, &total)) return tabled_refuse(c, why);
     *seek = nullptr;
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return seek_build_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, blocks, n_blocks, total, spacing, seek, report,
                           call_stream(c, hip_stream));
 }
@@ -480,17 +469,13 @@ int mi355_inflate_seek_build(mi355_deflate_ctx* c, const uint8_t* stream, size_t
     if (const char* why = seek_build_args(stream, stream_len, wrapper, blocks, n_blocks, spacing, seek, report, &total)) return tabled_refuse(c, why);
     *seek = nullptr;
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     uint8_t* d = nullptr;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), stream_len + 64));
-    hipStream_t st = c->own_stream;
-    hipError_t e = stream_len ? hipMemcpyAsync(d, stream, stream_len, hipMemcpyHostToDevice, st) : hipSuccess;
-    int rc = e == hipSuccess ? seek_build_one(c, d, stream_len, wrapper, blocks, n_blocks, total, spacing, seek, report, st) : fail_hip(c, "hipMemcpyAsync", e);
-    if (rc != MI355_OK) {
-        (void)hipStreamSynchronize(st);  // (the copy of the caller's buffer may be in flight)
+    int rc = stage_in(c, stream, stream_len, d);  // into a buffer the handle will own
+    if (rc == MI355_OK) rc = seek_build_one(c, d, stream_len, wrapper, blocks, n_blocks, total, spacing, seek, report, c->own_stream);
+    if (rc != MI355_OK) {  // (no handle for any failure, MI355_E_DATA among them)
+        stage_settle(c);
         (void)hipFree(d);
         return rc;
     }
@@ -521,10 +506,8 @@ int mi355_inflate_seek_read_batch_device(mi355_inflate_seek* h, const void* d_st
     const uint8_t* s = d_stream ? reinterpret_cast<const uint8_t*>(d_stream) : h->d_stream;
     if (!s && h->stream_len) return MI355_E_ARG;
     DefaultGuard dg_;
-    mi355_deflate_ctx* c = use_ctx(h->c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    mi355_deflate_ctx* c = h->c;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return seek_read_ranges(h, c, s, r, n, reports, call_stream(c, hip_stream));
 }
 
@@ -541,17 +524,14 @@ int mi355_inflate_seek_read_device(mi355_inflate_seek* h, const void* d_stream, 
 int mi355_inflate_seek_read(mi355_inflate_seek* h, uint64_t off, uint64_t len, uint8_t* out, uint64_t* got, mi355_inflate_report* report) {
     if (!h || !got || !report || (!out && len) || (!h->d_stream && h->stream_len)) return MI355_E_ARG;
     DefaultGuard dg_;
-    mi355_deflate_ctx* c = use_ctx(h->c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    mi355_deflate_ctx* c = h->c;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     const uint64_t room = is::is_got(off, len, h->total);
     if (const int rc = ensure_buf(c, &c->d_out, &c->d_out_cap, (size_t)room + 64)) return rc;
     mi355_seek_range r{off, len, c->d_out, 0, MI355_OK, 0u};
-    const int rc = seek_read_ranges(h, c, h->d_stream, &r, 1, report, c->own_stream);
-    if (rc != MI355_OK && rc != MI355_E_DATA) return rc;
-    if (r.got) HIPCHK(c, hipMemcpy(out, c->d_out, (size_t)r.got, hipMemcpyDeviceToHost));
-    *got = r.got;
+    int rc = seek_read_ranges(h, c, h->d_stream, &r, 1, report, c->own_stream);
+    rc = stage_out(c, rc, out, r.got);  // (nothing was staged in: the wait behind a hard error finds the stream idle)
+    if (rc == MI355_OK || rc == MI355_E_DATA) *got = r.got;
     return rc;
 }
 

@@ -210,7 +210,8 @@ int inflate_tabled_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t str
         *reinterpret_cast<IItem*>(c->v_host) = IItem{d_stream, stream_len, d_out, cap, c->d_sc, (uint32_t)wrapper, 0u};
         *reinterpret_cast<iw::Rec*>(c->v_host + rec_at) = acc;
         HIPCHK(c, hipMemcpyAsync(c->v_dev, c->v_host, rec_at + sizeof(iw::Rec), hipMemcpyHostToDevice, st));
-        rc = framed_tail(c, st, 1, rec_at, [&]() { return launch_sums_one(c, st, wrapper, d_out, acc.out_len); }, [&](int k) { return clk.mark(k); });
+        rc = framed_tail(c, st, 1, rec_at, [&]() { return launch_sums_one(c, st, wrapper, d_out, acc.out_len); },
+                         [&](int k) { return k < 2 ? clk.mark(k) : hipSuccess; });  // (one slot for the checksums and the trailer)
         if (rc) return rc;
         clk.lap(0, 1, 3);
         acc = *reinterpret_cast<const iw::Rec*>(c->v_host + rec_at);
@@ -233,10 +234,7 @@ int mi355_inflate_tabled_device(mi355_deflate_ctx* c, const void* d_stream, size
     if (const char* why = tabled_args(d_stream, stream_len, wrapper, blocks, n_blocks, d_out, out_cap, out_len, report, &total))
         return tabled_refuse(c, why);
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (const int rc = shard_refusal(c)) return rc;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return inflate_tabled_one(c, reinterpret_cast<const uint8_t*>(d_stream), stream_len, wrapper, blocks, n_blocks, total,
                               reinterpret_cast<uint8_t*>(d_out), out_cap, out_len, report, call_stream(c, hip_stream), &valid);
 }
@@ -257,8 +255,7 @@ int mi355_inflate_tabled(mi355_deflate_ctx* c, const uint8_t* stream, size_t str
     if (const char* why = tabled_args(stream, stream_len, wrapper, blocks, n_blocks, out, out_cap, out_len, report, &total))
         return tabled_refuse(c, why);
     DefaultGuard dg_;
-    c = use_ctx(c, dg_);
-    if (!c) return MI355_E_HIP;
+    if (const int rc = decode_enter(c, dg_)) return rc;
     return staged_call(c, stream, stream_len, out, out_cap, [&](const uint8_t* d_stream, uint8_t* d_out, hipStream_t st, uint64_t* valid) {
         return inflate_tabled_one(c, d_stream, stream_len, wrapper, blocks, n_blocks, total, d_out, out_cap, out_len, report, st, valid);
     });
