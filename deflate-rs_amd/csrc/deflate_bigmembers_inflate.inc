@@ -4,7 +4,7 @@
 //                           member's grid); span 0's workgroup leaves the member's head as well
 //   k_bigmember_walk        one workgroup of one wave per walker: k_index_walk's text with the extent's edge
 //   k_inflate_mtab          one workgroup of one wave per entry of a group: k_inflate_tab with the entry's part in hand
-//   k_inflate_mtab_window   one workgroup per PART: k_inflate_tab_window's step over the part's entries
+//   k_inflate_mtab_window   one workgroup per PART: the window walk (it_window_walk.inc) over the part's entries
 //   k_inflate_mtab_resolve  flat over the group's symbols -- the only kernel that writes `out`
 // Nothing waits inside a kernel.  The host side is MemberDev's (deflate_members_inflate.inc).  DESIGN.md section 15.
 #include "inflate_bigmembers.h"
@@ -56,9 +56,10 @@ __global__ __launch_bounds__(64) void k_inflate_mtab(const ib::Part* __restrict_
     if (threadIdx.x == 0) recs[blockIdx.x] = r;
 }
 
-// pass 2: the workgroup of part blockIdx.x walks the part's entries in order, two windows ping-ponged in LDS, from zeros -- a member
-// begins -- or from the window the group before left in slot 0.  Slot e + 1 gets the window behind entry e when the part's next entry
-// or the next group reads it.  It stops at the part's first failing entry and leaves the position up to which pass 3 may write.
+// pass 2: the workgroup of part blockIdx.x walks the part's entries in order (it_window_walk.inc), two windows ping-ponged in LDS, from
+// zeros -- a member begins -- or from the window the group before left in slot 0.  Slot e + 1 gets the window behind entry e when the
+// part's next entry or the next group reads it.  It stops at the part's first failing entry and leaves the position up to which pass
+// 3 may write.
 __global__ __launch_bounds__(1024) void k_inflate_mtab_window(const ib::Part* __restrict__ parts, const ic::Entry* __restrict__ ents,
                                                               const ic::Rec* __restrict__ recs, const uint16_t* __restrict__ sym, uint8_t* win,
                                                               uint32_t n_group, uint64_t* __restrict__ limits) {
@@ -70,40 +71,10 @@ __global__ __launch_bounds__(1024) void k_inflate_mtab_window(const ib::Part* __
         *reinterpret_cast<uint32_t*>(&s_w[0][j]) = pt.carried ? *reinterpret_cast<const uint32_t*>(win + (uint64_t)pt.e0 * it::WIN + j) : 0u;
     }
     __syncthreads();
-    const uint16_t* psym = sym + pt.sym_off;
-    const ic::Entry* pe = ents + pt.e0;
-    const ic::Rec* pr = recs + pt.e0;
-    uint32_t cur = 0;
-    uint64_t limit = pt.base;
-    uint32_t status = pt.n ? pr[0].status : 0;
-    uint64_t in_pos = pt.n ? pr[0].in_pos : 0, end_pos = pt.n ? pr[0].end_pos : 0, start = pt.n ? pe[0].pos : 0;
-    for (uint32_t k = 0; k < pt.n; k++) {
-        const uint32_t kn = k + 1 < pt.n ? k + 1 : k;
-        const uint32_t status_n = pr[kn].status;
-        const uint64_t in_pos_n = pr[kn].in_pos, end_pos_n = pr[kn].end_pos, start_n = pe[kn].pos;
-        if (status) {
-            limit = in_pos;
-            break;
-        }
-        limit = end_pos;
-        if (start < pt.cap) {  // (else it and everything behind it only counted)
-            const uint64_t len = end_pos - start;
-            const uint8_t* prev = s_w[cur];
-            uint8_t* next = s_w[cur ^ 1];
-            const bool kept = k + 1 < pt.n || pt.e0 + pt.n == n_group;
-            uint8_t* slot = win + (uint64_t)(pt.e0 + k + 1) * it::WIN;
-            for (uint32_t i = 0; i < it::WIN / 4096; i++) {
-                const uint32_t j = (tid + 1024 * i) * 4;
-                uint32_t v = 0;
-                for (uint32_t b = 0; b < 4; b++) v |= (uint32_t)it::it_window_byte(psym, pt.base, start, len, pt.cap, prev, j + b) << (8 * b);
-                *reinterpret_cast<uint32_t*>(next + j) = v;
-                if (kept) *reinterpret_cast<uint32_t*>(slot + j) = v;
-            }
-            __syncthreads();  // (one barrier a step, as in k_inflate_tab_window)
-            cur ^= 1;
-        }
-        status = status_n, in_pos = in_pos_n, end_pos = end_pos_n, start = start_n;
-    }
+    // (the window behind the part's last entry is always made, and stored only where the next group reads it)
+    const it::Walk wk{sym + pt.sym_off, ents + pt.e0, recs + pt.e0, pt.n, pt.base, pt.cap, win, pt.e0, n_group, true};
+    const WgWalk wp{tid};
+#include "it_window_walk.inc"
     if (tid == 0) limits[blockIdx.x] = limit;
 }
 

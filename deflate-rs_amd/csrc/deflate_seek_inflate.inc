@@ -5,7 +5,7 @@
 //                           from the group's workspace into the handle's store
 //   k_inflate_seek          pass 1, one workgroup of one wave per (range, entry): k_inflate_mtab's shape, the entry's part in hand
 //   k_inflate_seek_window   pass 2, one workgroup per part: the window of its point from the store (or zeros), then
-//                           k_inflate_mtab_window's step over the part's entries
+//                           the window walk (it_window_walk.inc) over the part's entries
 //   k_inflate_seek_resolve  pass 3, flat over the set's symbols -- the only kernel that writes `out`, and only [lo, min(limit, cap))
 // The build is the tabled inflate's passes 1 and 2 (k_inflate_tab, k_inflate_tab_window) group by group without an output buffer; a
 // framed stream's groups are resolved into a scratch region for the checksum launches.  The host driver's shared steps are in
@@ -44,8 +44,8 @@ __global__ __launch_bounds__(64) void k_inflate_seek(const is::Part* __restrict_
 }
 
 // pass 2: the workgroup of part blockIdx.x loads the window in front of its point -- kept by the build, or zeros in front of the
-// stream --, leaves it in the part's slot 0 for pass 3, and walks the part's entries in order, two windows ping-ponged in LDS.  Slot
-// k + 1 gets the window behind entry k when the part has an entry k + 1 to read it.  It stops at the part's first failing entry and
+// stream --, leaves it in the part's slot 0 for pass 3, and walks the part's entries in order (it_window_walk.inc), two windows in LDS.
+// Slot k + 1 gets the window behind entry k when the part has an entry k + 1 to read it.  It stops at the part's first failing entry and
 // leaves the position up to which pass 3 may write.
 __global__ __launch_bounds__(1024) void k_inflate_seek_window(const is::Part* __restrict__ parts, const ic::Entry* __restrict__ ents,
                                                               const ic::Rec* __restrict__ recs, const uint16_t* __restrict__ sym,
@@ -65,39 +65,10 @@ __global__ __launch_bounds__(1024) void k_inflate_seek_window(const is::Part* __
         }
     }
     __syncthreads();
-    const uint16_t* psym = sym + pt.sym_off;
-    const ic::Entry* pe = ents + pt.e0;
-    const ic::Rec* pr = recs + pt.e0;
-    uint32_t cur = 0;
-    uint64_t limit = pt.base;
-    uint32_t status = pt.n ? pr[0].status : 0;
-    uint64_t in_pos = pt.n ? pr[0].in_pos : 0, end_pos = pt.n ? pr[0].end_pos : 0, start = pt.n ? pe[0].pos : 0;
-    for (uint32_t k = 0; k < pt.n; k++) {
-        const uint32_t kn = k + 1 < pt.n ? k + 1 : k;
-        const uint32_t status_n = pr[kn].status;
-        const uint64_t in_pos_n = pr[kn].in_pos, end_pos_n = pr[kn].end_pos, start_n = pe[kn].pos;
-        if (status) {
-            limit = in_pos;
-            break;
-        }
-        limit = end_pos;
-        if (k + 1 < pt.n && start < pt.cap) {  // (the window behind the part's last entry is nobody's)
-            const uint64_t len = end_pos - start;
-            const uint8_t* prev = s_w[cur];
-            uint8_t* next = s_w[cur ^ 1];
-            uint8_t* slot = win + (uint64_t)(pt.w0 + k + 1) * it::WIN;
-            for (uint32_t i = 0; i < it::WIN / 4096; i++) {
-                const uint32_t j = (tid + 1024 * i) * 4;
-                uint32_t v = 0;
-                for (uint32_t b = 0; b < 4; b++) v |= (uint32_t)it::it_window_byte(psym, pt.base, start, len, pt.cap, prev, j + b) << (8 * b);
-                *reinterpret_cast<uint32_t*>(next + j) = v;
-                *reinterpret_cast<uint32_t*>(slot + j) = v;
-            }
-            __syncthreads();  // (one barrier a step, as in k_inflate_tab_window)
-            cur ^= 1;
-        }
-        status = status_n, in_pos = in_pos_n, end_pos = end_pos_n, start = start_n;
-    }
+    // (the window behind the part's last entry is nobody's: it is not made)
+    const it::Walk wk{sym + pt.sym_off, ents + pt.e0, recs + pt.e0, pt.n, pt.base, pt.cap, win, pt.w0, pt.w0 + pt.n, false};
+    const WgWalk wp{tid};
+#include "it_window_walk.inc"
     if (tid == 0) limits[blockIdx.x] = limit;
 }
 
@@ -289,7 +260,7 @@ int seek_build_one(mi355_deflate_ctx* c, const uint8_t* d_stream, size_t stream_
         }
         if (wrapper && stored) {
             hipLaunchKernelGGL(k_inflate_seek_resolve, dim3(cdiv(stored, 256 * it::RESOLVE_RUN)), dim3(256), 0, st,
-                               reinterpret_cast<const is::Part*>(c->v_dev + part_at), 1u, d_ents, d_lim, item.sym, c->t_dev, is::is_align(stored));
+                               reinterpret_cast<const is::Part*>(c->v_dev + part_at), 1u, d_ents, d_lim, item.sym, c->t_dev, it::it_align(stored));
             HIPCHK(c, hipGetLastError());
             // (a group that holds a failure: the sums of what lies in the scratch region are never used)
             rc = launch_sums_one(c, st, wrapper, scratch, stored);

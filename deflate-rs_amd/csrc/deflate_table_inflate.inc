@@ -52,9 +52,17 @@ __global__ __launch_bounds__(64) void k_inflate_tab(const TItem it, const ic::En
     if (threadIdx.x == 0) recs[blockIdx.x] = r;
 }
 
-// pass 2: ONE workgroup walks the group's entries in order, two windows ping-ponged in LDS; a step reads the window in front of the
-// entry from LDS and the entry's symbols, which pass 1 wrote: no global store of this kernel is read back by it.  It stops at the
-// first failing entry and leaves the position up to which pass 3 may write.
+// a thread's part in the window walk of a workgroup of 1024 (it_window_walk.inc): eight of a window's 8192 words, and the barrier
+struct WgWalk {
+    static constexpr uint32_t turns = it::WIN / 4096;
+    uint32_t tid;
+    __device__ uint32_t word(uint32_t i) const { return (tid + 1024 * i) * 4; }
+    __device__ void step_done(uint32_t) const { __syncthreads(); }
+};
+
+// pass 2: ONE workgroup walks the group's entries in order (it_window_walk.inc), two windows ping-ponged in LDS; a step reads the
+// window in front of the entry from LDS and the entry's symbols, which pass 1 wrote: no global store of this kernel is read back by
+// it.  It stops at the first failing entry and leaves the position up to which pass 3 may write.
 __global__ __launch_bounds__(1024) void k_inflate_tab_window(const TItem it, const ic::Entry* __restrict__ ents, const ic::Rec* __restrict__ recs,
                                                              uint64_t* __restrict__ limit_out) {
     __shared__ __attribute__((aligned(16))) uint8_t s_w[2][it::WIN];
@@ -64,38 +72,9 @@ __global__ __launch_bounds__(1024) void k_inflate_tab_window(const TItem it, con
         *reinterpret_cast<uint32_t*>(&s_w[0][j]) = *reinterpret_cast<const uint32_t*>(it.win + j);
     }
     __syncthreads();
-    uint32_t cur = 0;
-    uint64_t limit = it.base;
-    // what a step needs of its entry -- status, out_pos, end, start: the same in every thread, so the branches below are the
-    // workgroup's -- is loaded a step ahead, off the chain
-    uint32_t status = it.n ? recs[0].status : 0;
-    uint64_t in_pos = it.n ? recs[0].in_pos : 0, end_pos = it.n ? recs[0].end_pos : 0, start = it.n ? ents[0].pos : 0;
-    for (uint32_t k = 0; k < it.n; k++) {
-        const uint32_t kn = k + 1 < it.n ? k + 1 : k;
-        const uint32_t status_n = recs[kn].status;
-        const uint64_t in_pos_n = recs[kn].in_pos, end_pos_n = recs[kn].end_pos, start_n = ents[kn].pos;
-        if (status) {
-            limit = in_pos;
-            break;
-        }
-        limit = end_pos;
-        if (start < it.cap) {  // (else it and everything behind it only counted)
-            const uint64_t len = end_pos - start;
-            const uint8_t* prev = s_w[cur];
-            uint8_t* next = s_w[cur ^ 1];
-            uint8_t* slot = it.win + (uint64_t)(k + 1) * it::WIN;
-            for (uint32_t i = 0; i < it::WIN / 4096; i++) {
-                const uint32_t j = (tid + 1024 * i) * 4;
-                uint32_t v = 0;
-                for (uint32_t b = 0; b < 4; b++) v |= (uint32_t)it::it_window_byte(it.sym, it.base, start, len, it.cap, prev, j + b) << (8 * b);
-                *reinterpret_cast<uint32_t*>(next + j) = v;
-                *reinterpret_cast<uint32_t*>(slot + j) = v;
-            }
-            __syncthreads();  // (one barrier a step: the window written in this step is not written again before the step after next)
-            cur ^= 1;
-        }
-        status = status_n, in_pos = in_pos_n, end_pos = end_pos_n, start = start_n;
-    }
+    const it::Walk wk{it.sym, ents, recs, it.n, it.base, it.cap, it.win, 0u, it.n, true};  // (every window is made and stored)
+    const WgWalk wp{tid};
+#include "it_window_walk.inc"
     if (tid == 0) *limit_out = limit;
 }
 
@@ -104,7 +83,7 @@ __global__ __launch_bounds__(256) void k_inflate_tab_resolve(const TItem it, con
                                                              uint8_t* __restrict__ out) {
     const uint64_t lim = *limit;
     const uint64_t q0 = it.base + ((uint64_t)blockIdx.x * 256 + threadIdx.x) * it::RESOLVE_RUN;
-    it::it_resolve_run(it.sym, it.win, ents, it.n, it.base, lim < it.cap ? lim : it.cap, out, q0);
+    it::it_resolve_run(it.sym, it.win, ents, it.n, it.base, lim < it.cap ? lim : it.cap, 0, out, q0);
 }
 
 }  // namespace mi355

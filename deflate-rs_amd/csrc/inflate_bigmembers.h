@@ -93,7 +93,6 @@ struct Rules {
     static MI355_IC uint64_t origin(uint64_t p) { return 0 * p; }                        // where a member's positions begin to count
 };
 
-MI355_IC uint64_t ib_align(uint64_t v) { return (v + it::RESOLVE_RUN - 1) / it::RESOLVE_RUN * it::RESOLVE_RUN; }
 // the spans of a member's first extent: the threshold's worth, one at least ...
 MI355_IC uint64_t ib_first_extent(uint64_t threshold, uint64_t S) {
     const uint64_t e = threshold / S;
@@ -146,26 +145,15 @@ MI355_IC void ib_decode_entry(Tables& t, uint16_t* sym, const Part& pt, const En
     it::Sink o{sym + pt.sym_off, nullptr, pt.base, e.pos, pt.cap, e.pos};
     it::it_entry<P>(t, pt.data, pt.nbytes, o, e, pt.total, r);
 }
-// pass 3: the part that holds symbol element f0 -- the last one that begins at or before it (parts without symbols in front of it
-// begin there too)
-MI355_IC uint32_t ib_part_of(const Part* parts, uint32_t n, uint64_t f0) {
-    uint32_t lo = 0, hi = n;
-    for (uint32_t guard = 0; guard < 32 && hi - lo > 1; guard++) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (parts[mid].sym_off <= f0) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-// ... and one resolve step: RESOLVE_RUN symbols from element f0 on (a multiple of RESOLVE_RUN, so inside one part)
+// pass 3: one resolve step: RESOLVE_RUN symbols from element f0 on (a multiple of RESOLVE_RUN, so inside one part)
 MI355_IC void ib_resolve_run(const uint16_t* sym, const uint8_t* win, const Entry* ents, const Part* parts, uint32_t n_parts,
                              const uint64_t* limits, uint64_t f0) {
     if (!n_parts) return;
-    const uint32_t j = ib_part_of(parts, n_parts, f0);
+    const uint32_t j = it::it_part_of(parts, n_parts, f0);
     const Part& pt = parts[j];
     if (f0 < pt.sym_off || !pt.n) return;
     const uint64_t lim = limits[j];
-    it::it_resolve_run(sym + pt.sym_off, win + (uint64_t)pt.e0 * it::WIN, ents + pt.e0, pt.n, pt.base, lim < pt.cap ? lim : pt.cap, pt.out,
+    it::it_resolve_run(sym + pt.sym_off, win + (uint64_t)pt.e0 * it::WIN, ents + pt.e0, pt.n, pt.base, lim < pt.cap ? lim : pt.cap, 0, pt.out,
                        pt.base + (f0 - pt.sym_off));
 }
 
@@ -250,7 +238,7 @@ inline void ib_plan(const std::vector<Found>& found, const std::vector<Entry>& a
         const Entry& e = g.ents[pt.e0 + pt.n - 1];
         const uint64_t end = e.last ? pt.total : e.next_pos;
         const uint64_t stored = pt.base < pt.cap ? (end < pt.cap ? end : pt.cap) - pt.base : 0;
-        g.syms += ib_align(stored);
+        g.syms += it::it_align(stored);
     };
     for (uint64_t f = k0; f < k1; f++) {
         const uint32_t m = all[f].item;

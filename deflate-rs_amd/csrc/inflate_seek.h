@@ -78,7 +78,6 @@ struct Counts {
     uint64_t entries, symbols, steps, sets;
 };
 
-MI355_IC uint64_t is_align(uint64_t v) { return (v + it::RESOLVE_RUN - 1) / it::RESOLVE_RUN * it::RESOLVE_RUN; }
 // pread's count
 MI355_IC uint64_t is_got(uint64_t off, uint64_t len, uint64_t total) { return off >= total ? 0 : (len < total - off ? len : total - off); }
 
@@ -90,56 +89,25 @@ MI355_IC void is_decode_entry(Tables& t, uint16_t* sym, const Part& pt, const En
     it::it_decode_entry<P>(t, pt.stream, pt.stream_len, pt.wrapper, o, e, pt.total, r);
 }
 
-// pass 3: it_resolve_run's sibling with a lower bound: out[q - lo] for q in [max(q0, lo), end) of the run.  The aligned fast path is
-// judged on the address the run's first byte goes to; a run that begins below lo goes byte by byte and forms no pointer below out.
+// pass 3's earlier name.  Nothing in this tree uses it: host builds written against the earlier headers (tests/inflseek and
+// tests/inflcut of the commit before) do, and it can go once none is left.
 template <class R>
 MI355_IC void is_resolve_run(const uint16_t* sym, const uint8_t* win, const Entry* ents, uint32_t n, uint64_t base, uint64_t end, uint64_t lo,
                              uint8_t* out, uint64_t q0) {
-    if (q0 >= end || !n) return;
-    const uint32_t cnt = end - q0 < it::RESOLVE_RUN ? (uint32_t)(end - q0) : it::RESOLVE_RUN;
-    if (!R::writes(q0 + cnt - 1, lo)) return;  // the whole run is lead-in
-    uint32_t k = it::it_entry_of(ents, n, q0);
-    uint8_t v[it::RESOLVE_RUN];
-    for (uint32_t i = 0; i < it::RESOLVE_RUN; i++) {
-        v[i] = 0;
-        if (i >= cnt) continue;
-        const uint64_t q = q0 + i;
-        for (uint32_t guard = 0; guard < it::RESOLVE_RUN && k + 1 < n && ents[k + 1].pos <= q; guard++) k = it::it_entry_of(ents, n, q);
-        const uint32_t s = sym[q - base];
-        v[i] = s < it::MARK ? (uint8_t)s : win[(uint64_t)k * it::WIN + ((s - it::MARK) & (it::WIN - 1))];
-    }
-    if (cnt == it::RESOLVE_RUN && R::writes(q0, lo) && (((uintptr_t)out + (q0 - lo)) & 7) == 0) {
-        uint64_t a, b;
-        __builtin_memcpy(&a, v, 8);
-        __builtin_memcpy(&b, v + 8, 8);
-        uint64_t* d = (uint64_t*)__builtin_assume_aligned(out + (q0 - lo), 8);
-        d[0] = a, d[1] = b;
-        return;
-    }
-    for (uint32_t i = 0; i < it::RESOLVE_RUN; i++)
-        if (i < cnt && R::writes(q0 + i, lo)) out[q0 + i - lo] = v[i];
+    it::it_resolve_run<R>(sym, win, ents, n, base, end, lo, out, q0);
 }
-// the part that holds symbol element f0 (ib_part_of's rule)
-MI355_IC uint32_t is_part_of(const Part* parts, uint32_t n, uint64_t f0) {
-    uint32_t lo = 0, hi = n;
-    for (uint32_t guard = 0; guard < 32 && hi - lo > 1; guard++) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (parts[mid].sym_off <= f0) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-// ... and one resolve step of a set: RESOLVE_RUN symbols from element f0 on (a multiple of RESOLVE_RUN, so inside one part)
+// one resolve step of a set: RESOLVE_RUN symbols from element f0 on (a multiple of RESOLVE_RUN, so inside one part), through
+// it_resolve_run with the part's lower bound
 template <class R>
 MI355_IC void is_resolve_set(const uint16_t* sym, const uint8_t* win, const Entry* ents, const Part* parts, uint32_t n_parts,
                              const uint64_t* limits, uint64_t f0) {
     if (!n_parts) return;
-    const uint32_t j = is_part_of(parts, n_parts, f0);
+    const uint32_t j = it::it_part_of(parts, n_parts, f0);
     const Part& pt = parts[j];
     if (f0 < pt.sym_off || !pt.n) return;
     const uint64_t lim = limits[j];
-    is_resolve_run<R>(sym + pt.sym_off, win + (uint64_t)pt.w0 * it::WIN, ents + pt.e0, pt.n, pt.base, lim < pt.cap ? lim : pt.cap, pt.lo, pt.out,
-                      pt.base + (f0 - pt.sym_off));
+    it::it_resolve_run<R>(sym + pt.sym_off, win + (uint64_t)pt.w0 * it::WIN, ents + pt.e0, pt.n, pt.base, lim < pt.cap ? lim : pt.cap, pt.lo,
+                          pt.out, pt.base + (f0 - pt.sym_off));
 }
 
 // ---- host side of all builds ------------------------------------------------------------------------------------------------------
@@ -189,7 +157,7 @@ inline void is_plan(const Entry* ents, uint64_t n, uint64_t total, const std::ve
                 if (point_pos(c) < pe) pe = point_pos(c);
             }
             const uint32_t a = pts[i], b = it::it_entry_of(ents, (uint32_t)n, pe - 1);  // (pe > cur >= base: b >= a)
-            const uint64_t syms = is_align(pe - base);
+            const uint64_t syms = it::it_align(pe - base);
             if (sets.empty() || (!sets.back().parts.empty() && sets.back().syms + syms > budget)) sets.emplace_back();
             Set& s = sets.back();
             s.parts.push_back(Part{stream, stream_len, ranges[r].out + (cur - off), cur, pe, total, base, s.syms, (uint32_t)s.ents.size(), b - a + 1,

@@ -21,6 +21,10 @@
 #ifndef MI355_INFLATE_TABLE_H
 #define MI355_INFLATE_TABLE_H
 
+#include <string.h>
+
+#include <vector>
+
 #include "inflate_write.h"
 
 namespace mi355 {
@@ -270,8 +274,22 @@ MI355_IC uint8_t it_window_byte(const uint16_t* sym, uint64_t base, uint64_t sta
     }
     return prev[j + (uint32_t)len];
 }
+// one chain of entries, as the walk over it (it_window_walk.inc) takes it
+struct Walk {
+    const uint16_t* sym;  // element 0 is output position `base`
+    const Entry* ents;
+    const ic::Rec* recs;
+    uint32_t n;
+    uint64_t base, cap;
+    uint8_t* win;        // the windows' slots: slot0 + k + 1 is the window behind entry k
+    uint32_t slot0;
+    uint32_t last_slot;  // the workspace's last slot, the one the next group reads: the window behind the chain's last entry is stored
+                         // only where that is its slot (the windows behind the other entries always are)
+    bool last_made;      // false: the window behind the chain's last entry is not made at all
+};
 
 // ---- pass 3: one resolve step, RESOLVE_RUN output bytes from q0 on, below `end` = min(limit, cap) -------------------------------------
+MI355_IC uint64_t it_align(uint64_t v) { return (v + RESOLVE_RUN - 1) / RESOLVE_RUN * RESOLVE_RUN; }
 // the entry of the group that holds position q: the last one that begins at or before it (the empty ones in front of it begin there too)
 MI355_IC uint32_t it_entry_of(const Entry* ents, uint32_t n, uint64_t q) {
     uint32_t lo = 0, hi = n;
@@ -282,11 +300,31 @@ MI355_IC uint32_t it_entry_of(const Entry* ents, uint32_t n, uint64_t q) {
     }
     return lo;
 }
-// win: the group's windows, slot k = the window in front of entry k (W_{k-1}; slot 0 comes from the group before)
-MI355_IC void it_resolve_run(const uint16_t* sym, const uint8_t* win, const Entry* ents, uint32_t n, uint64_t base, uint64_t end, uint8_t* out,
-                             uint64_t q0) {
+// the part that holds symbol element f0 (is::Part, ib::Part): the last one that begins at or before it (parts without symbols in front
+// of it begin there too)
+template <class Part>
+MI355_IC uint32_t it_part_of(const Part* parts, uint32_t n, uint64_t f0) {
+    uint32_t lo = 0, hi = n;
+    for (uint32_t guard = 0; guard < 32 && hi - lo > 1; guard++) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (parts[mid].sym_off <= f0) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// pass 3's lower bound (a seek read's lead-in is decoded and never written; the tabled and the members callers have none: lo = 0)
+struct Writes {
+    static MI355_IC bool writes(uint64_t q, uint64_t lo) { return q >= lo; }
+};
+// win: the group's windows, slot k = the window in front of entry k (W_{k-1}; slot 0 comes from the group before).  out[q - lo] for q
+// in [max(q0, lo), end) of the run.  The aligned fast path is judged on the address the run's first byte goes to; a run that begins
+// below lo goes byte by byte and forms no pointer below out.
+template <class R = Writes>
+MI355_IC void it_resolve_run(const uint16_t* sym, const uint8_t* win, const Entry* ents, uint32_t n, uint64_t base, uint64_t end, uint64_t lo,
+                             uint8_t* out, uint64_t q0) {
     if (q0 >= end || !n) return;
     const uint32_t cnt = end - q0 < RESOLVE_RUN ? (uint32_t)(end - q0) : RESOLVE_RUN;
+    if (!R::writes(q0 + cnt - 1, lo)) return;  // the whole run is lead-in
     uint32_t k = it_entry_of(ents, n, q0);
     uint8_t v[RESOLVE_RUN];
     for (uint32_t i = 0; i < RESOLVE_RUN; i++) {
@@ -297,16 +335,22 @@ MI355_IC void it_resolve_run(const uint16_t* sym, const uint8_t* win, const Entr
         const uint32_t s = sym[q - base];
         v[i] = s < MARK ? (uint8_t)s : win[(uint64_t)k * WIN + ((s - MARK) & (WIN - 1))];
     }
-    if (cnt == RESOLVE_RUN && (((uintptr_t)out + q0) & 7) == 0) {
+    if (cnt == RESOLVE_RUN && R::writes(q0, lo) && (((uintptr_t)out + (q0 - lo)) & 7) == 0) {
         uint64_t a, b;
         __builtin_memcpy(&a, v, 8);
         __builtin_memcpy(&b, v + 8, 8);
-        uint64_t* d = (uint64_t*)__builtin_assume_aligned(out + q0, 8);
+        uint64_t* d = (uint64_t*)__builtin_assume_aligned(out + (q0 - lo), 8);
         d[0] = a, d[1] = b;
         return;
     }
     for (uint32_t i = 0; i < RESOLVE_RUN; i++)
-        if (i < cnt) out[q0 + i] = v[i];
+        if (i < cnt && R::writes(q0 + i, lo)) out[q0 + i - lo] = v[i];
+}
+// the call form from before the lower bound.  Nothing in this tree uses it: host builds written against the earlier headers
+// (tests/infltable of the commit before) do, and it can go once none is left.
+MI355_IC void it_resolve_run(const uint16_t* sym, const uint8_t* win, const Entry* ents, uint32_t n, uint64_t base, uint64_t end, uint8_t* out,
+                             uint64_t q0) {
+    it_resolve_run(sym, win, ents, n, base, end, 0, out, q0);
 }
 
 // ---- host side of all builds ------------------------------------------------------------------------------------------------------
@@ -345,6 +389,29 @@ MI355_IC uint64_t it_limit(const ic::Rec* recs, uint32_t n, uint64_t base) {
         limit = recs[k].end_pos;
     }
     return limit;
+}
+// ... and the walk itself for the host builds: the text the three window kernels run, by one caller that takes every word of a
+// window and needs no barrier; `step(k)` is called where the workgroup's barrier stands.  first: the window in front of entry 0
+// (nullptr: zeros).  It returns the walk's limit.  The text stores a window a 32-bit word at a time: wk.win must be 4-byte aligned
+// (the two windows here are, as vectors' storage).
+template <class Step>
+struct SerialWalk {
+    static constexpr uint32_t turns = WIN / 4;
+    Step& step;
+    uint32_t word(uint32_t i) const { return 4 * i; }
+    void step_done(uint32_t k) const { step(k); }
+};
+template <class Step>
+inline uint64_t it_window_walk(const Walk& wk, const uint8_t* first, Step&& step) {
+    std::vector<uint8_t> w[2] = {std::vector<uint8_t>(WIN, 0), std::vector<uint8_t>(WIN)};
+    if (first) memcpy(w[0].data(), first, WIN);
+    uint8_t* const s_w[2] = {w[0].data(), w[1].data()};
+    const SerialWalk<Step> wp{step};
+#include "it_window_walk.inc"
+    return limit;
+}
+inline uint64_t it_window_walk(const Walk& wk, const uint8_t* first) {
+    return it_window_walk(wk, first, [](uint32_t) {});
 }
 
 }  // namespace it

@@ -111,31 +111,13 @@ struct BigBe : HostBe<Lanes<0>> {
         }
         // pass 1: every entry on its own (any order would do)
         for (uint32_t e = k; e-- > 0;) ib::ib_decode_entry<TabP>(t, sym.p, g.parts[g.ents[e].item], g.ents[e], got[e]);
-        // pass 2: a window chain per part, two windows ping-ponged (LDS in the kernel)
+        // pass 2: the kernel's walk per part, from the carried window or from zeros
         for (uint32_t j = np; j-- > 0;) {
             const ib::Part& pt = g.parts[j];
-            std::vector<uint8_t> w[2] = {std::vector<uint8_t>(it::WIN, 0), std::vector<uint8_t>(it::WIN, 0)};
-            if (pt.carried) memcpy(w[0].data(), win.p + (size_t)pt.e0 * it::WIN, it::WIN);
-            uint32_t cur = 0;
-            uint64_t limit = pt.base;
-            for (uint32_t i = 0; i < pt.n; i++) {
-                const ic::Rec& r = got[pt.e0 + i];
-                if (r.status) {
-                    limit = r.in_pos;
-                    break;
-                }
-                limit = r.end_pos;
-                const uint64_t start = g.ents[pt.e0 + i].pos;
-                if (start >= pt.cap) continue;
-                const bool kept = i + 1 < pt.n || pt.e0 + pt.n == k;
-                for (uint32_t b = 0; b < it::WIN; b++) {
-                    const uint8_t v = it::it_window_byte(sym.p + pt.sym_off, pt.base, start, r.end_pos - start, pt.cap, w[cur].data(), b);
-                    w[cur ^ 1][b] = v;
-                    if (kept) win.p[(size_t)(pt.e0 + i + 1) * it::WIN + b] = v;
-                }
-                cur ^= 1;
-            }
-            limits.p[j] = limit;
+            const ic::Rec* pr = got.data() + pt.e0;
+            const it::Walk wk{sym.p + pt.sym_off, g.ents.data() + pt.e0, pr, pt.n, pt.base, pt.cap, win.p, pt.e0, k, true};
+            limits.p[j] = it::it_window_walk(wk, pt.carried ? win.p + (size_t)pt.e0 * it::WIN : nullptr);
+            if (limits.p[j] != it::it_limit(pr, pt.n, pt.base)) abort();  // (the walk and the header's statement of its rule agree)
         }
         // pass 3: the only writes of `out`
         for (uint64_t f0 = 0; f0 < g.syms; f0 += it::RESOLVE_RUN) ib::ib_resolve_run(sym.p, win.p, g.ents.data(), g.parts.data(), np, limits.p, f0);

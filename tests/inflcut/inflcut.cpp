@@ -134,10 +134,6 @@ struct Handle {
     int mutant = 0, serial = 0;
 };
 
-void window_step(const uint16_t* sym, uint64_t base, uint64_t start, uint64_t len, uint64_t cap, const uint8_t* prev, uint8_t* next, uint8_t* slot) {
-    for (uint32_t j = 0; j < it::WIN; j++) next[j] = slot[j] = it::it_window_byte(sym, base, start, len, cap, prev, j);
-}
-
 // the build as deflate_seek_inflate.inc drives it (tests/inflseek's run_build); with cuts, pass 1 is k_inflate_tab_cut's
 template <class P, class R>
 void run_build(Handle& h, const uint8_t* s, const uint64_t* in_bytes, uint64_t group_bytes, iw::Rec& acc) {
@@ -179,20 +175,14 @@ void run_build(Handle& h, const uint8_t* s, const uint64_t* in_bytes, uint64_t g
             n_cut[k] = r.n_cuts < ns ? r.n_cuts : ns;
             h.surplus += r.n_cuts > ns ? r.n_cuts - ns : 0;
         }
-        std::vector<uint8_t> w[2] = {std::vector<uint8_t>(win.p, win.p + it::WIN), std::vector<uint8_t>(it::WIN)};
-        uint32_t cur = 0;
-        for (uint32_t k = 0; k < n && !recs[k].status; k++) {
-            if (ge[k].pos >= total) continue;
-            window_step(sym.p, base, ge[k].pos, recs[k].end_pos - ge[k].pos, total, w[cur].data(), w[cur ^ 1].data(), win.p + (size_t)(k + 1) * it::WIN);
-            cur ^= 1;
-        }
-        const uint64_t limit = it::it_limit(recs.data(), n, base);
+        const uint64_t limit = it::it_window_walk(it::Walk{sym.p, ge, recs.data(), n, base, total, win.p, 0u, n, true}, win.p);  // k_inflate_tab_window
+        if (limit != it::it_limit(recs.data(), n, base)) abort();  // (the walk and the header's statement of its rule agree)
         for (; next_pt < h.pts.size() && h.pts[next_pt] < k1; next_pt++)
             memcpy(h.store.data() + (next_pt - 1) * (size_t)it::WIN, win.p + (size_t)(h.pts[next_pt] - k0) * it::WIN, it::WIN);
         if (h.wrapper && stored) {
             const uint64_t end = limit < base + stored ? limit : base + stored;
             for (uint64_t q0 = base; q0 < base + stored; q0 += it::RESOLVE_RUN)
-                is::is_resolve_run<is::Rules>(sym.p, win.p, ge, n, base, end, base, scratch.p, q0);
+                it::it_resolve_run<is::Rules>(sym.p, win.p, ge, n, base, end, base, scratch.p, q0);
         }
         carry.assign(win.p + (size_t)n * it::WIN, win.p + (size_t)(n + 1) * it::WIN);
         if (!it::it_report(recs.data(), n, acc)) return;
@@ -263,26 +253,12 @@ void run_set(const Handle& h, const is::Set& s, std::vector<ic::Rec>& recs, icut
     std::vector<uint64_t> limits(np);
     for (size_t j = 0; j < np; j++) {  // pass 2: a workgroup per part
         const is::Part& pt = s.parts[j];
-        std::vector<uint8_t> w[2] = {std::vector<uint8_t>(it::WIN, 0), std::vector<uint8_t>(it::WIN)};
-        if (pt.wslot != is::WSLOT_ZEROS) memcpy(w[0].data(), h.store.data() + (size_t)pt.wslot * it::WIN, it::WIN);
-        memcpy(win.p + (size_t)pt.w0 * it::WIN, w[0].data(), it::WIN);
-        const ic::Entry* pe = s.ents.data() + pt.e0;
+        uint8_t* w0 = win.p + (size_t)pt.w0 * it::WIN;  // the point's window, left in the part's slot 0
+        if (pt.wslot != is::WSLOT_ZEROS) memcpy(w0, h.store.data() + (size_t)pt.wslot * it::WIN, it::WIN);
+        else memset(w0, 0, it::WIN);
         const ic::Rec* pr = recs.data() + pt.e0;
-        uint32_t cur = 0;
-        uint64_t limit = pt.base;
-        for (uint32_t k = 0; k < pt.n; k++) {
-            if (pr[k].status) {
-                limit = pr[k].in_pos;
-                break;
-            }
-            limit = pr[k].end_pos;
-            if (k + 1 < pt.n && pe[k].pos < pt.cap) {
-                window_step(sym.p + pt.sym_off, pt.base, pe[k].pos, pr[k].end_pos - pe[k].pos, pt.cap, w[cur].data(), w[cur ^ 1].data(),
-                            win.p + (size_t)(pt.w0 + k + 1) * it::WIN);
-                cur ^= 1;
-            }
-        }
-        limits[j] = limit;
+        limits[j] = it::it_window_walk(it::Walk{sym.p + pt.sym_off, s.ents.data() + pt.e0, pr, pt.n, pt.base, pt.cap, win.p, pt.w0, pt.w0 + pt.n, false}, w0);
+        if (limits[j] != it::it_limit(pr, pt.n, pt.base)) abort();  // (the walk and the header's statement of its rule agree)
     }
     for (uint64_t f0 = 0; f0 < s.syms; f0 += it::RESOLVE_RUN)  // pass 3: the only writes of `out`
         is::is_resolve_set<is::Rules>(sym.p, win.p, s.ents.data(), s.parts.data(), (uint32_t)np, limits.data(), f0);

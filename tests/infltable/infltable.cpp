@@ -172,25 +172,13 @@ void run_three(const uint8_t* s, uint64_t stream_len, uint32_t wrapper, const st
             LaneTab::fenced() = ge[k].pos;
             it::it_decode_entry<LaneTab>(t, s, stream_len, wrapper, o, ge[k], total, recs[k]);
         }
-        // pass 2: the windows, two of them ping-ponged (LDS in the kernel), each also written to its slot
-        std::vector<uint8_t> w[2] = {std::vector<uint8_t>(win.p, win.p + it::WIN), std::vector<uint8_t>(it::WIN)};
+        // pass 2: the kernel's walk, every window to its slot; behind each step, it_window_byte's case split once more for the depth
         std::vector<uint32_t> dep[2] = {carry_dep, std::vector<uint32_t>(it::WIN)};
         uint32_t cur = 0;
-        uint64_t limit = base;
-        for (uint32_t k = 0; k < n; k++) {
-            if (recs[k].status) {
-                limit = recs[k].in_pos;
-                break;
-            }
-            limit = recs[k].end_pos;
-            const uint64_t start = ge[k].pos;
-            if (start >= cap) continue;
-            const uint64_t len = recs[k].end_pos - start;
+        const it::Walk wk{sym.p, ge, recs.data(), n, base, cap, win.p, 0u, n, true};
+        const uint64_t limit = it::it_window_walk(wk, win.p, [&](uint32_t k) {
+            const uint64_t start = ge[k].pos, len = recs[k].end_pos - start;
             for (uint32_t j = 0; j < it::WIN; j++) {
-                const uint8_t v = it::it_window_byte(sym.p, base, start, len, cap, w[cur].data(), j);
-                w[cur ^ 1][j] = v;
-                win.p[(size_t)(k + 1) * it::WIN + j] = v;
-                // the same case split, for the depth
                 uint32_t d = 0;
                 if (len >= it::WIN || j >= it::WIN - len) {
                     const uint64_t q = start + len + j - it::WIN;
@@ -202,11 +190,11 @@ void run_three(const uint8_t* s, uint64_t stream_len, uint32_t wrapper, const st
                 if (q_is_live(start, len, j) && d > g_carry_depth) g_carry_depth = d;
             }
             cur ^= 1;
-        }
-        if (limit != it::it_limit(recs.data(), n, base)) abort();  // (the kernel's loop and the header's function agree)
+        });
+        if (limit != it::it_limit(recs.data(), n, base)) abort();  // (the walk and the header's statement of its rule agree)
         // pass 3: the only writes of `out`
         const uint64_t end = limit < cap ? limit : cap;
-        for (uint64_t q0 = base; q0 < base + stored; q0 += it::RESOLVE_RUN) it::it_resolve_run(sym.p, win.p, ge, n, base, end, out, q0);
+        for (uint64_t q0 = base; q0 < base + stored; q0 += it::RESOLVE_RUN) it::it_resolve_run(sym.p, win.p, ge, n, base, end, 0, out, q0);
         carry.assign(win.p + (size_t)n * it::WIN, win.p + (size_t)(n + 1) * it::WIN);  // (the driver's copy of the last slot)
         carry_dep = dep[cur];
         if (!it::it_report(recs.data(), n, acc)) return;
