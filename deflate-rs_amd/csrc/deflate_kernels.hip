@@ -3600,6 +3600,7 @@ __global__ void k_gzip_frame(DevScalars* sc, uint8_t* out, const uint8_t* hdr, u
 #include "deflate_bgzf.inc"
 #include "deflate_verify.inc"
 #include "deflate_inflate.inc"
+#include "deflate_stream_inflate.inc"
 #include "deflate_table_inflate.inc"
 #include "deflate_index_inflate.inc"
 #include "deflate_bigmembers_inflate.inc"

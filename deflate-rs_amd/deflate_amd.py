@@ -217,6 +217,17 @@ class BgzfInfo(C.Structure):
                 ("max_out_len", C.c_uint64)]
 
 
+class InflateStreamState(C.Structure):
+    """mi355_inflate_stream_state (48 bytes)"""
+    _fields_ = [("total_in", C.c_uint64), ("total_out", C.c_uint64), ("pending_in", C.c_uint64), ("need_out", C.c_uint64),
+                ("done", C.c_uint32), ("failed", C.c_uint32), ("adler_or_crc", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in InflateStreamState._fields_ if k != "reserved"}
+        d["failed"] = VERIFY_STATUS[self.failed] if self.failed < len(VERIFY_STATUS) else self.failed
+        return d
+
+
 class DeflateError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mi355_deflate error %d: %s" % (code, msg))
@@ -400,6 +411,18 @@ def load():
                                                C.c_void_p]
     L.mi355_bgzf_last_read.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mi355_bgzf_last_read_stages.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.mi355_inflate_stream_new.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mi355_inflate_stream_write.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                             C.POINTER(InflateReport)]
+    L.mi355_inflate_stream_write_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                    C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_stream_write_batch_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BatchItem), C.c_size_t,
+                                                          C.POINTER(InflateReport), C.c_void_p]
+    L.mi355_inflate_stream_finish.argtypes = [C.c_void_p, C.POINTER(InflateReport)]
+    L.mi355_inflate_stream_state_get.argtypes = [C.c_void_p, C.POINTER(InflateStreamState)]
+    L.mi355_inflate_stream_reset.argtypes = [C.c_void_p]
+    L.mi355_inflate_stream_free.argtypes = [C.c_void_p]
+    L.mi355_inflate_stream_free.restype = None
     _lib = L
     return L
 
@@ -440,7 +463,107 @@ EXPORTED = [
     "mi355_bgzf_index_build", "mi355_bgzf_index_build_device", "mi355_bgzf_index_from_members", "mi355_bgzf_index_free",
     "mi355_bgzf_index_info", "mi355_bgzf_index_members", "mi355_bgzf_voffset", "mi355_bgzf_uoffset",
     "mi355_bgzf_read", "mi355_bgzf_read_device", "mi355_bgzf_read_batch_device", "mi355_bgzf_last_read", "mi355_bgzf_last_read_stages",
+    "mi355_inflate_stream_new", "mi355_inflate_stream_write", "mi355_inflate_stream_write_device",
+    "mi355_inflate_stream_write_batch_device", "mi355_inflate_stream_finish", "mi355_inflate_stream_state_get",
+    "mi355_inflate_stream_reset", "mi355_inflate_stream_free",
 ]
+
+
+class InflateStream:
+    """A streaming inflate handle (mi355_inflate_stream): zlib's decompressobj on the device.  Made by Context.inflate_stream.  The
+    granularity is the deflate block: write() returns the bytes of every block that has become complete."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._h = ctx, handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load().mi355_inflate_stream_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def write_raw(self, chunk, room):
+        """mi355_inflate_stream_write on host bytes: (rc, the bytes handed over, report dict); rc is OK, E_DATA, E_OUT_TOO_SMALL or
+        E_STATE, anything else raises.  room 0 hands the decoder a NULL buffer (the query form)."""
+        chunk = bytes(chunk)
+        buf = C.create_string_buffer(room) if room else None
+        n = C.c_size_t(0)
+        r = InflateReport()
+        rc = load().mi355_inflate_stream_write(self._h, chunk if chunk else None, len(chunk), C.cast(buf, C.c_void_p) if room else None, room,
+                                               C.byref(n), C.byref(r))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL, E_STATE):
+            self._ctx._err(rc)
+        return rc, (buf.raw[: n.value] if room else b""), r.as_dict()
+
+    def write(self, chunk, room=None):
+        """The stream's next bytes after `chunk` (possibly none: more input is needed).  room None: the buffer starts at eight times
+        the chunk and the write is repeated with state()["need_out"] for as long as a complete block waits for room; a given room
+        is used as it is, and DeflateError(E_OUT_TOO_SMALL, ...) says that the next block does not fit.  Raises DeflateError(E_DATA,
+        ...) for a stream that is not valid -- the bytes in front of the failure are the exception's `partial` -- and
+        DeflateError(E_STATE, ...) for a dead handle."""
+        out, cap = [], (max(8 * len(chunk), 4096) if room is None else room)
+        while True:
+            rc, data, _rep = self.write_raw(chunk, cap)
+            chunk = b""
+            out.append(data)
+            need = self.state()["need_out"]
+            if rc in (OK, E_OUT_TOO_SMALL) and room is None and need:
+                cap = need
+                continue
+            if rc != OK:
+                try:
+                    self._ctx._err(rc)
+                except DeflateError as e:
+                    e.partial = b"".join(out)
+                    raise
+            return b"".join(out)
+
+    def write_device(self, d_in_ptr, in_len, d_out_ptr, out_cap, stream=0):
+        """mi355_inflate_stream_write_device: device pointers.  Returns (rc, out_len, report dict); rc as in write_raw."""
+        n = C.c_size_t(0)
+        r = InflateReport()
+        rc = load().mi355_inflate_stream_write_device(self._h, C.c_void_p(d_in_ptr), in_len, C.c_void_p(d_out_ptr), out_cap, C.byref(n),
+                                                      C.byref(r), C.c_void_p(stream))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL, E_STATE):
+            self._ctx._err(rc)
+        return rc, n.value, r.as_dict()
+
+    def finish_raw(self):
+        """mi355_inflate_stream_finish: (rc, report dict); OK, E_DATA (FRAME / TRUNCATED) or E_STATE"""
+        r = InflateReport()
+        rc = load().mi355_inflate_stream_finish(self._h, C.byref(r))
+        if rc not in (OK, E_DATA, E_STATE):
+            self._ctx._err(rc)
+        return rc, r.as_dict()
+
+    def finish(self):
+        """No more input will come: raises DeflateError(E_DATA, ...) unless the stream is done"""
+        rc, _rep = self.finish_raw()
+        if rc != OK:
+            self._ctx._err(rc)
+
+    def state(self):
+        """mi355_inflate_stream_state_get as a dict"""
+        s = InflateStreamState()
+        rc = load().mi355_inflate_stream_state_get(self._h, C.byref(s))
+        if rc != OK:
+            self._ctx._err(rc)
+        return s.as_dict()
+
+    @property
+    def done(self):
+        return bool(self.state()["done"])
+
+    def reset(self):
+        """Same wrapper and dictionary, a new stream; revives a dead handle"""
+        rc = load().mi355_inflate_stream_reset(self._h)
+        if rc != OK:
+            self._ctx._err(rc)
 
 
 class SeekIndex:
@@ -1479,6 +1602,67 @@ class Context:
         out = InflateReports(reps[k].as_dict() for k in range(n))
         out.items = items
         return rc, out
+
+    # ---- streaming inflate (mi355_inflate_stream_*) ----
+    def inflate_stream(self, wrapper=0, zdict=None):
+        """A streaming inflate handle on this context.  zdict: a preset dictionary (raw streams only)."""
+        h = C.c_void_p()
+        zdict = bytes(zdict) if zdict else None
+        rc = load().mi355_inflate_stream_new(self._h, wrapper, zdict, len(zdict) if zdict else 0, C.byref(h))
+        if rc != OK:
+            if rc == E_ARG:
+                raise DeflateError(rc, "inflate stream: wrapper must be 0, 1 or 2, and a dictionary goes with wrapper 0 only")
+            self._err(rc)
+        return InflateStream(self, h)
+
+    def inflate_stream_write_batch_device(self, streams, items, stream=0):
+        """mi355_inflate_stream_write_batch_device.  streams: InflateStream handles; items: a BatchItem array, or a list of (chunk
+        pointer, chunk length, buffer pointer, buffer size) with an optional fifth element, the status on entry.  Returns (rc, report
+        dicts); out_len and status are written into the array, the second element's `items` attribute."""
+        n = len(streams)
+        if not isinstance(items, C.Array):
+            arr = (BatchItem * max(n, 1))()
+            for k, it in enumerate(items):
+                arr[k].in_, arr[k].in_len, arr[k].out, arr[k].out_cap = C.c_void_p(it[0]), it[1], C.c_void_p(it[2]), it[3]
+                arr[k].status = it[4] if len(it) > 4 else OK
+            items = arr
+        hs = (C.c_void_p * max(n, 1))(*[s._h for s in streams])
+        reps = (InflateReport * max(n, 1))()
+        rc = load().mi355_inflate_stream_write_batch_device(self._h, hs, items, n, reps, C.c_void_p(stream))
+        if rc not in (OK, E_DATA, E_OUT_TOO_SMALL, E_STATE):
+            self._err(rc)
+        out = InflateReports(reps[k].as_dict() for k in range(n))
+        out.items = items
+        return rc, out
+
+    def inflate_stream_write_batch(self, streams, chunks, room=None):
+        """One chunk of host bytes for each handle, all through one call: [bytes], the next bytes of every stream.  room None:
+        eight times the chunk (4096 at least) each; handles whose next block waits for room are written again, alone, with what
+        their state asks for.  Raises DeflateError at the first handle that fails."""
+        import torch
+
+        dev = "cuda:%d" % self.device
+        chunks = [bytes(c) for c in chunks]
+        rooms = [max(8 * len(c), 4096) if room is None else room for c in chunks]
+        d_in = torch.frombuffer(bytearray(b"".join(chunks)) or bytearray(1), dtype=torch.uint8).to(dev)
+        d_out = torch.empty(max(sum(rooms), 1), dtype=torch.uint8, device=dev)
+        items, a, b = [], 0, 0
+        for c, r in zip(chunks, rooms):
+            items.append((d_in.data_ptr() + a if c else 0, len(c), d_out.data_ptr() + b if r else 0, r))
+            a, b = a + len(c), b + r
+        rc, reps = self.inflate_stream_write_batch_device(streams, items)
+        host = d_out.cpu().numpy().tobytes()
+        out, b = [], 0
+        for k, r in enumerate(rooms):
+            out.append(host[b:b + reps.items[k].out_len])
+            b += r
+        for k, s in enumerate(streams):
+            st = reps.items[k].status
+            if st in (OK, E_OUT_TOO_SMALL) and room is None and s.state()["need_out"]:
+                out[k] += s.write(b"")
+            elif st != OK:
+                raise DeflateError(st, "inflate stream: item %d: %s" % (k, reps[k]["status"]))
+        return out
 
     def batch_info(self):
         """mi355_deflate_last_batch_info as a dict"""

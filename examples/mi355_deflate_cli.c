@@ -2,7 +2,7 @@
  * binds): compresses a file on the GPU, or with -d decompresses one.
  *   mi355_deflate_cli [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT
  *   mi355_deflate_cli --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT
- *   mi355_deflate_cli -d [--parallel] [-raw|-zlib|-gzip] IN OUT
+ *   mi355_deflate_cli -d [--parallel | --chunk N] [-raw|-zlib|-gzip] IN OUT
  *   mi355_deflate_cli -d --members [-gzip] IN OUT
  *   mi355_deflate_cli -d --members --range OFF:LEN [-gzip] IN OUT
  *   mi355_deflate_cli -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT
@@ -16,7 +16,9 @@
  * -d / --decompress inflates IN (a raw, zlib or gzip stream by the format switch) to OUT on the GPU: mi355_inflate once without a
  * buffer for the size, once more for the bytes; exits with status 3 and the report if the stream is not valid.  With --parallel the
  * two calls are mi355_inflate_parallel: the block table of the stream is found on the GPU and every entry decoded by a wave of its own
- * (the way for one large file from anywhere); the result is the same.  With --members IN is a gzip FILE of any number of members --
+ * (the way for one large file from anywhere); the result is the same.  With --chunk N the file goes N bytes at a time through a stream
+ * handle (mi355_inflate_stream_write: what a receiver of a connection does), every write's bytes straight to OUT; the result is the
+ * same, and --chunk does not go with --parallel, --members or --range.  With --members IN is a gzip FILE of any number of members --
  * BGZF, `cat a.gz b.gz` -- and the two calls are mi355_inflate_members (plain -d -gzip takes exactly one member); --members with -raw or -zlib is refused with the usage text.
  * With --range OFF:LEN only the bytes [OFF, OFF + LEN) of what IN inflates to are written (fewer at its end, like pread): a seek index
  * is built (mi355_inflate_seek_build: the table found on the GPU, a window kept every MiB of output) and the range is decoded from the
@@ -75,14 +77,14 @@ int main(int argc, char** argv) {
             char* end = NULL;
             block = strtoull(argv[++a], &end, 10);
             block_given = end && end != argv[a] && !*end && block >= 1 && block <= 65280 ? 1 : -1;
-        } else if (!strcmp(argv[a], "-chunk") && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
+        } else if ((!strcmp(argv[a], "-chunk") || !strcmp(argv[a], "--chunk")) && a + 1 < argc) chunk = strtoull(argv[++a], NULL, 10);
         else break;
     }
     /* --members is gzip by definition: another format switch beside it is refused, not ignored */
     if (argc - a != 2 || ((parallel || members || ranged) && !decompress) || (parallel && members) || (members && format_given && wrapper != 2) ||
         ranged < 0 || (ranged && parallel) || cut_given < 0 || (cut_given && (!ranged || members)) || block_given < 0 || (block_given && !bgzf) ||
-        (bgzf && (decompress || format_given || chunk))) {
-        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT\n       %s -d [--parallel] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --members --range OFF:LEN [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
+        (bgzf && (decompress || format_given || chunk)) || (decompress && chunk && (parallel || members || ranged))) {
+        fprintf(stderr, "usage: %s [-raw|-zlib|-gzip] [-fast|-default|-best] [-chunk N] [--verify] IN OUT\n       %s --bgzf [--block N] [-fast|-default|-best] [--verify] IN OUT\n       %s -d [--parallel | --chunk N] [-raw|-zlib|-gzip] IN OUT\n       %s -d --members [-gzip] IN OUT\n       %s -d --members --range OFF:LEN [-gzip] IN OUT\n       %s -d --range OFF:LEN [--cut BYTES] [-raw|-zlib|-gzip] IN OUT\n",
                 argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
@@ -98,6 +100,55 @@ int main(int argc, char** argv) {
     mi355_deflate_ctx* ctx = NULL;
     int rc = mi355_deflate_ctx_create(0, &ctx);
     if (rc) return fail("mi355_deflate_ctx_create (no GPU? there is no CPU fallback)", rc, NULL);
+    if (decompress && chunk) { /* a stream handle, fed N bytes at a time; a block that waits for room gets the room the state names */
+        mi355_inflate_stream* is = NULL;
+        mi355_inflate_stream_state st;
+        mi355_inflate_report r;
+        size_t cap = 8 * chunk > 65536 ? 8 * chunk : 65536, total = 0, writes = 0;
+        uint8_t* data = (uint8_t*)malloc(cap);
+        if (!data) return fail("malloc", -1, NULL);
+        rc = mi355_inflate_stream_new(ctx, wrapper, NULL, 0, &is);
+        if (rc) return fail("mi355_inflate_stream_new", rc, ctx);
+        f = fopen(argv[a + 1], "wb");
+        if (!f) return fail("write output", -1, NULL);
+        for (size_t i = 0; rc == MI355_OK && (i < n || i == 0); i += chunk) {
+            size_t k = n - i < chunk ? n - i : chunk, fed = 0;
+            do { /* again without input while a complete block waits for room */
+                size_t got = 0;
+                rc = mi355_inflate_stream_write(is, fed ? NULL : in + i, fed ? 0 : k, data, cap, &got, &r);
+                fed = 1, writes++;
+                if (rc != MI355_OK && rc != MI355_E_OUT_TOO_SMALL && rc != MI355_E_DATA) return fail("mi355_inflate_stream_write", rc, ctx);
+                if (fwrite(data, 1, got, f) != got) return fail("write output", -1, NULL);
+                total += got;
+                mi355_inflate_stream_state_get(is, &st);
+                if (rc != MI355_E_DATA && st.need_out) {
+                    if (st.need_out > cap) {
+                        free(data);
+                        cap = (size_t)st.need_out;
+                        data = (uint8_t*)malloc(cap);
+                        if (!data) return fail("malloc", -1, NULL);
+                    }
+                    rc = MI355_OK;
+                }
+            } while (rc == MI355_OK && st.need_out);
+        }
+        if (rc == MI355_OK) rc = mi355_inflate_stream_finish(is, &r);
+        fclose(f);
+        if (rc == MI355_E_DATA) {
+            fprintf(stderr, "inflate: status %u at bit %llu, output byte %llu\n%s\n", r.status, (unsigned long long)r.bit,
+                    (unsigned long long)r.out_pos, mi355_deflate_last_error(ctx));
+            return 3;
+        }
+        if (rc) return fail("mi355_inflate_stream_finish", rc, ctx);
+        mi355_inflate_stream_state_get(is, &st);
+        fprintf(stderr, "%lu -> %lu bytes in %lu writes of %lu bytes, checksum %08x\n", (unsigned long)n, (unsigned long)total, (unsigned long)writes,
+                (unsigned long)chunk, st.adler_or_crc);
+        mi355_inflate_stream_free(is);
+        free(data);
+        free(in);
+        mi355_deflate_ctx_destroy(ctx);
+        return 0;
+    }
     if (decompress && members && ranged) { /* a BGZF file: its member index from its own claims, then the members that hold the range */
         mi355_inflate_report r;
         mi355_bgzf_index* idx = NULL;

@@ -899,6 +899,71 @@ int mi355_bgzf_read_batch_device(mi355_deflate_ctx* ctx, const mi355_bgzf_index*
 int mi355_bgzf_last_read(mi355_deflate_ctx* ctx, uint64_t v[6]);
 int mi355_bgzf_last_read_stages(mi355_deflate_ctx* ctx, float ms[3]);
 
+/* ---- streaming inflate: decode a stream as it arrives, piece by piece ---------------------------------------------------
+ * zlib's inflate() with Z_SYNC_FLUSH: the receiving end of mi355_deflate_stream_flush, of a MI355_FLUSH_SYNC chunk, of a long-lived
+ * compressed connection.  A handle (mi355_inflate_stream) belongs to a context and holds, in DEVICE memory, the compressed bytes it
+ * could not use yet -- everything from the byte that holds the COMMIT POINT, the end of the last block it handed over -- and a pair of
+ * 32 KiB history buffers; on the host the totals, the running Adler-32 / CRC-32 and its state.
+ * _new: wrapper 0 / 1 / 2 as everywhere, anything else MI355_E_ARG.  dict (host memory, may be NULL with dict_len 0): a preset
+ *   dictionary for a RAW stream, the last 32768 bytes of which are the history in front of the first byte; dict_len > 0 with wrapper
+ *   1 or 2 is MI355_E_ARG (a zlib stream with FDICT stays MI355_VERIFY_FRAME).  ONE gzip member.
+ * A WRITE appends in[0, in_len) to the pending bytes, decodes from the commit point and hands over the bytes of every block that has
+ *   become complete and fits:
+ *   MI355_OK               out[0, *out_len) are the stream's next bytes; *out_len may be 0 (more input is needed); report.out_pos =
+ *                          the bytes handed over since the stream began (state.total_out), report.out_len = *out_len.  If the write
+ *                          committed some blocks and found the next complete one too large, state.need_out says what room suffices.
+ *   MI355_E_OUT_TOO_SMALL  the next complete block does not fit and nothing could be committed: *out_len = 0, state.need_out = the
+ *                          room that suffices (exact: the decode went on counting).  The input WAS taken: write(NULL, 0, a bigger
+ *                          buffer) goes on.  out_cap == 0 with out == NULL is the query form.
+ *   MI355_E_DATA           the report is mi355_inflate's: status, the ABSOLUTE raw-deflate bit and the absolute out_pos of the first
+ *                          failing element; out[0, *out_len) holds the bytes in front of it that were not handed over before (the
+ *                          prefix that fits out_cap).  The handle is dead: every later write and _finish is MI355_E_STATE until
+ *                          _reset.  The checksum of a framed stream (MI355_VERIFY_CHECKSUM, Adler-32 / CRC-32 / ISIZE mod 2^32) is
+ *                          judged at the write that completes the trailer, whose bytes are handed over all the same.
+ *   After the stream's end (state.done) a write of 0 bytes is MI355_OK and bytes behind the end are MI355_E_DATA with
+ *   MI355_VERIFY_TRAILER -- the one-shot's single-member rule; so are bytes behind the trailer in the write that completes it.
+ *   No store lands in out at an index >= out_cap.  What runs out of input is never an error of a write: a header, a code, extra
+ *   bits, a stored piece that is not all there yet leaves the handle waiting at its commit point.
+ * GRANULARITY is the deflate block: a partial block is decoded again by the next write from its first bit, and none of its bytes is
+ *   handed over before it is complete (the BFINAL block: before its trailer is).  The FLUSH GUARANTEE follows: after a write whose
+ *   input ends at or behind a complete empty stored block (00 00 FF FF), or behind any block end, every byte the encoder had taken
+ *   before that point has been handed over, given the room.  One wave walks a handle's bytes, so this is made for MANY handles with
+ *   a small message each (_write_batch_device); one large stream belongs to mi355_inflate_parallel.
+ * _finish: no more input will come.  MI355_OK if the stream is done; else MI355_E_DATA with MI355_VERIFY_FRAME (the header never
+ *   completed) or MI355_VERIFY_TRUNCATED at the first element that could not be completed -- the deflate data is taken to be
+ *   everything behind the header --, and the handle is dead.
+ * _state_get: total_in (bytes written), total_out (bytes handed over), pending_in (compressed bytes held), need_out, done, failed
+ *   (the MI355_VERIFY_* the handle died of), adler_or_crc (of the bytes handed over: Adler-32 for wrapper 1, CRC-32 for 2, 0 for 0).
+ * _reset: same context, wrapper and dictionary, a new stream; revives a dead handle.  _free: NULL is fine.
+ * _write_device: device pointers for in and out; hip_stream NULL = the context's stream; the call returns after it has drained.  A
+ *   write of a raw stream is one launch and one wait: the wave also leaves the next history.  A framed write waits a second time when
+ *   bytes were handed over: the encode's checksum kernels over them, folded on the host with mi355_checksum_combine.
+ * _write_batch_device: items[i].in / in_len is the chunk for s[i], out / out_cap its room (device pointers); out_len and status are
+ *   written, and reports[i] if reports is not NULL.  Items whose status on entry is not MI355_OK are skipped and left alone.  The
+ *   handles must be distinct, not NULL and belong to ctx (ctx NULL: to the default context), else MI355_E_ARG before anything is
+ *   touched.  One decode launch for all, one workgroup per handle; a failing or starved handle disturbs no neighbour; a dead handle's
+ *   item gets MI355_E_STATE; the call returns the first failing item's status.
+ * MI355_E_ARG is decided before the device is touched: a NULL handle, report or out_len, in == NULL with in_len > 0, out == NULL with
+ *   out_cap > 0, a bad wrapper in _new.  A live shard on the handle's context is MI355_E_STATE.  More than 4 GiB - 64 KiB pending is
+ *   MI355_E_UNSUPPORTED.  A stream write leaves mi355_deflate_last_info / _last_blocks / _last_batch_info alone;
+ *   mi355_deflate_last_error of the handle's context gives one line.  A handle must be freed before its context is destroyed. */
+typedef struct mi355_inflate_stream mi355_inflate_stream; /* owns: pending bytes and two 32 KiB histories (device) */
+typedef struct {
+    uint64_t total_in, total_out, pending_in, need_out;
+    uint32_t done, failed, adler_or_crc, reserved;
+} mi355_inflate_stream_state; /* 48 bytes */
+int mi355_inflate_stream_new(mi355_deflate_ctx* ctx, int wrapper, const uint8_t* dict, size_t dict_len, mi355_inflate_stream** out);
+int mi355_inflate_stream_write(mi355_inflate_stream* s, const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap, size_t* out_len,
+                               mi355_inflate_report* report);
+int mi355_inflate_stream_write_device(mi355_inflate_stream* s, const void* d_in, size_t in_len, void* d_out, size_t out_cap,
+                                      size_t* out_len, mi355_inflate_report* report, void* hip_stream);
+int mi355_inflate_stream_write_batch_device(mi355_deflate_ctx* ctx, mi355_inflate_stream* const* s, mi355_batch_item* items, size_t n,
+                                            mi355_inflate_report* reports /* n entries, or NULL */, void* hip_stream);
+int mi355_inflate_stream_finish(mi355_inflate_stream* s, mi355_inflate_report* report); /* no more input will come */
+int mi355_inflate_stream_state_get(mi355_inflate_stream* s, mi355_inflate_stream_state* state);
+int mi355_inflate_stream_reset(mi355_inflate_stream* s); /* same wrapper and dictionary, a new stream */
+void mi355_inflate_stream_free(mi355_inflate_stream* s);
+
 /* ---- sharded encode: ONE input over several GPUs, stream-exact (P1) ---------------------------
  * Rank r holds in device memory the bytes [global_lo, global_lo + n_ext) of the input: its own range
  * [parse_lo, parse_hi) (buffer coordinates; parse_lo = 32768 of history except on the first rank,
